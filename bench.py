@@ -9,9 +9,15 @@ GT -> BoxEvaluator counters, all on the device.  N GPUs = N independent clips
 (frame-sharded data parallelism, weak scaling); the only collective is the
 final all-reduce of the BoxEvaluator counters.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (with the
+conv roofline read from the timed steps' own launches).  ``--full`` adds the measurements
+that take runs of their own: the one-stream conv pass, the forward / bbox breakdown, the
+other conv precision, the 250-tau and forward-only rates and the CPU baseline.
+``--dump-outputs DIR`` writes what the last timed step computed as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -308,6 +314,31 @@ def side_rates(model, comp, xd, td, gd, frames: int, steps: int, fwd_streams: in
     return {"valid_250tau": v, "forward_only": f}
 
 
+def dump_outputs(path: str, comp, cam_u8) -> None:
+    """What a caller of the timed path holds after its last step, as ``path``/<name>.npy:
+    the clip's uint8 CAMs (the return value of ``CAMComputer.evaluate_batch``), its float
+    CAMs and logits, and the BoxEvaluator counters, which have accumulated every clip since
+    start-up (warm-up included).  float32, counters float64; ~13 MB at the default clip.  A
+    clip whose two CAM arrays would exceed 48 MB is cut to a fixed, seeded choice of its
+    frames (``frames.npy`` lists them)."""
+    ev = comp.evaluator
+    b = int(cam_u8.shape[0])
+    keep = max(1, (48 << 20) // (2 * 4 * int(cam_u8[0].numel())))
+    idx = np.arange(b) if b <= keep else np.sort(np.random.default_rng(0).choice(b, keep, False))
+    sel = torch.from_numpy(idx).to(cam_u8.device)
+    arrays = {
+        "frames": sel.double(),
+        "cam_u8": cam_u8[sel].float(),
+        "cam": comp.last_cam[sel].float(),
+        "logits": comp.last_logits[sel].float(),
+        "box_counters": ev.counters.double(),
+        "cls_correct": ev.cls_correct.double(),
+    }
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().cpu().numpy())
+
+
 def launch_ranks(n: int) -> int:
     """One rank per GPU via torch.distributed.run (rendezvous on 127.0.0.1), run as a
     child process; returns its exit status."""
@@ -330,8 +361,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--frames", type=int, default=32, help="frames per clip per GPU")
     ap.add_argument("--interval", type=float, default=0.001, help="cam_curve_interval")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (one-stream conv pass, forward / bbox "
+                         "breakdown, other conv precision, 250-tau and forward-only rates, CPU "
+                         "baseline); a plain run reports the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays of the last timed step (uint8 CAMs, float CAMs, "
+                         "logits, evaluator counters) as DIR/<name>.npy (rank 0)")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--precision", default=os.environ.get("TCAM_CONV_PRECISION", "f16x3"),
                     choices=("f16x3", "x6", "fp32"),
                     help="f16x3: fp16-split MFMA convs on S2 (default); x6: exact bf16-split "
@@ -339,13 +378,16 @@ def main():
     ap.add_argument("--fwd-streams", type=int, default=int(os.environ.get("TCAM_FWD_STREAMS", 2)),
                     help="forward streams pipelining consecutive clips (CAMComputer)")
     ap.add_argument("--no-alt", action="store_true",
-                    help="skip the short side measurement of the other conv precision")
+                    help="with --full: skip the short side measurement of the other conv "
+                         "precision")
     ap.add_argument("--timer-window", type=int, default=5,
                     help="clips of the timed region whose conv launches carry the roofline's "
                          "HIP events (the middle ones; 0 = all)")
     ap.add_argument("--no-roofline-timer", action="store_true",
                     help="time the headline run without per-launch HIP events")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N`: start the N ranks here (one process per GPU) as
@@ -403,7 +445,7 @@ def main():
         if timer is not None and i == w0:
             ops.set_launch_timer(timer)
         n0 = len(timer) if timer is not None else 0
-        comp.evaluate_batch(xd, td, gd)
+        cam_u8 = comp.evaluate_batch(xd, td, gd)
         if timer is not None and w0 <= i < w0 + win:
             clips.append((n0, len(timer)))
         if timer is not None and i == w0 + win - 1:
@@ -423,6 +465,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # before any side measurement reuses the model's output buffers
+        dump_outputs(args.dump_outputs, comp, cam_u8)
 
     frames_total = args.frames * args.steps * world
     value = frames_total / elapsed
@@ -435,11 +480,12 @@ def main():
                             f"(every conv launch of those clips, both forward streams, HIP "
                             f"events bound to the dispatches; busy time and FLOPs taken over "
                             f"the span in which only those clips run)")
-        roof["isolated_one_stream"] = isolated_conv_pass(comp, xd, td, gd)
-    brk = breakdown_pass(model, comp, xd, td, gd)
+        if args.full:
+            roof["isolated_one_stream"] = isolated_conv_pass(comp, xd, td, gd)
+    brk = breakdown_pass(model, comp, xd, td, gd) if args.full else None
 
     alt = None
-    if world == 1 and not args.no_alt:
+    if args.full and world == 1 and not args.no_alt:
         # the other conv precision, same workload, short run (reported beside)
         other = "x6" if args.precision != "x6" else "f16x3"
         model.conv_precision = other
@@ -460,16 +506,18 @@ def main():
         model.conv_precision = args.precision
 
     # the side rates over the headline's own step count, so that they compare with it
-    rates = side_rates(model, comp, xd, td, gd, args.frames, args.steps, args.fwd_streams)
+    rates = {}
+    if args.full:
+        rates = side_rates(model, comp, xd, td, gd, args.frames, args.steps, args.fwd_streams)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(model, x, targets, gt, comp.cam_threshold_list, args.cpu_budget)
 
     if rank == 0:
         out = {
             "metric": METRIC, "value": round(value, 2), "unit": "frames/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup,
+            "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "fp32",

@@ -5,7 +5,7 @@
 #
 #   tests                pytest -m gpu ($PYTEST_FILES, default tests/; $PYTEST_K: -k filter)
 #   smoke                __graft_entry__.smoke()
-#   bench                bench.py headline line (N=1)            -> gpurun_out/bench.json
+#   bench                bench.py --full: headline line (N=1) with its side measurements, on stdout
 #   prof                 rocprofv3 --kernel-trace --stats of the exact headline command
 #                        (2 forward streams)                     -> gpurun_out/prof/
 #   pmc                  PMC passes over the headline command: FETCH_SIZE, WRITE_SIZE,
@@ -39,8 +39,7 @@ run_step() {
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1
     rc=$?; tail -2 gpurun_out/smoke.log; return $rc ;;
   bench)
-    timeout -k 10 400 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err
-    rc=$?; cat gpurun_out/bench.json; return $rc ;;
+    timeout -k 10 400 python bench.py --full ;;
   prof)
     mkdir -p gpurun_out/prof
     timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o bench \
