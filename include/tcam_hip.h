@@ -560,13 +560,18 @@ int tcam_bn_relu_s2(const void* y, const float* mean, const float* invstd, const
 int tcam_bn_relu_bwd_s3s2(const void* dout, const void* out, const void* y, const float* mean,
                           const float* invstd, const float* gamma, void* dy, float* dgamma,
                           float* dbeta, long P, int C, void* ws, uint32_t* amax, void* stream);
-/* dy (S3) -> scale[c] (power of two, max |dy_c| scale in [2^14, 2^15)) and dy2 = its scaled
- * S2 copy (P x C x 4 B).  amax: from tcam_bn_relu_bwd_s3s2, or computed here (compute = 1). */
+/* dy (S3) -> scale[c] (power of two, max |dy_c| scale in [2^14, 2^15), the exponent clamped
+ * to [-126, 126]) and dy2 = its scaled S2 copy (P x C x 4 B).  An all-zero channel gets the
+ * top of the clamp, 2^126 (1 for a non-finite one): dy2_c and dW_c stay exactly 0, and the
+ * data gradient's operand W[c] / scale[c] (tcam_pack_weight_f16x3 kdiv) loses that channel's
+ * weights instead of letting them set the fp16 range of every packed column.  amax: from
+ * tcam_bn_relu_bwd_s3s2, or computed here (compute = 1: C / 8 must divide 256). */
 int tcam_dy_scaled_s2(const void* dy, long P, int C, uint32_t* amax, int compute, float* scale,
                       void* dy2, void* stream);
 /* The same backward fused with the scaled copy (round 6): dy2 (S2) = dy * scale[c] with
  * scale[c] a power of two from the bound |dy_c| <= |gamma invstd| (max|g| + |mean g| +
- * max|xhat| |mean g xhat|) (max |dy_c| scale < 2^15, no max pass); dy3 (S3 dy, or NULL).
+ * max|xhat| |mean g xhat|) (max |dy_c| scale < 2^15, no max pass; a zero bound — every dy_c
+ * is 0 — gives 2^126, as tcam_dy_scaled_s2 gives an all-zero channel); dy3 (S3 dy, or NULL).
  * out NULL: the ReLU mask is recomputed from y (gamma xhat + beta > 0 as tcam_bn_relu_s2
  * computes it, an fma) — a BN-ReLU; else out's sign (the Bottleneck tail).  C / 8 must
  * divide 256.  ws: tcam_bn_bwd_scaled_ws_bytes(P, C). */

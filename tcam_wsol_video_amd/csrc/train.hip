@@ -114,6 +114,14 @@ __global__ __launch_bounds__(kB) void bn_relu_kernel(const uint8_t* __restrict__
     L::store(out + i * L::GB, v);
 }
 
+// xhat of the sum g * xhat in fp64: the fp32 roundings of xhat (2^-24 |xhat| each) do not
+// cancel in the sum when its terms do, so a channel whose sum g xhat is a small remainder of
+// sum |g xhat| would get a dgamma, and through mean(g xhat) a dy, with that much less
+// relative accuracy (measured 7e-5 of the magnitudes of dy's own terms at 2048 x 70).
+__device__ __forceinline__ double xhat64(float y, float mean, float invstd) {
+    return ((double)y - (double)mean) * (double)invstd;
+}
+
 // backward partials: sum g and sum g * xhat (g = dout masked by relu(out) > 0).
 // L: the layout of the gradients (dout, dy); LA: of the forward's activations (out, y) —
 // the f16x3 training step keeps activations in S2 and gradients in S3.
@@ -140,9 +148,8 @@ __global__ __launch_bounds__(kB) void bn_bwd_partial_kernel(
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float gg = o.v[e] > 0.f ? d.v[e] : 0.f;
-            const float xh = (v.v[e] - mu[e]) * is[e];
             s[e] += (double)gg;
-            q[e] += (double)gg * (double)xh;
+            q[e] += (double)gg * xhat64(v.v[e], mu[e], is[e]);
         }
     }
     __shared__ double red[kB / 64][16];
@@ -197,9 +204,8 @@ __global__ __launch_bounds__(kB) void bn_bwd_partial_co_kernel(
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float gg = o.v[e] > 0.f ? d.v[e] : 0.f;
-            const float xh = (v.v[e] - mu[e]) * is[e];
             s[e] += (double)gg;
-            q[e] += (double)gg * (double)xh;
+            q[e] += (double)gg * xhat64(v.v[e], mu[e], is[e]);
         }
     }
     __shared__ double red[kB][17];
@@ -292,7 +298,14 @@ __global__ __launch_bounds__(kB) void bn_bwd_apply_amax_kernel(
         for (int e = 0; e < 8; ++e) {
             const float gg = o.v[e] > 0.f ? d.v[e] : 0.f;
             const float xh = (v.v[e] - cm[e]) * ci[e];
-            r.v[e] = cg[e] * (gg - c0[e] - xh * c1[e]);
+            const float t = gg - c0[e] - xh * c1[e];
+            {
+                // the product rounded to fp32 before the store splits it: contracted into the
+                // split's x - hi (an fma on the unrounded product) the written dy can differ
+                // from r by an ulp, and amax must be the maximum of the dy that was written
+#pragma clang fp contract(off)
+                r.v[e] = cg[e] * t;
+            }
             m[e] = fmaxf(m[e], fabsf(r.v[e]));
         }
         L::store(dy + i * L::GB, r);
@@ -374,7 +387,10 @@ __global__ __launch_bounds__(kB) void bn_bwd_finalize_sc_kernel(
     const double n = (double)P;
     const double bound = fabs((double)gamma[c] * (double)invstd[c]) *
                          ((double)gmx + fabs(s) / n + (double)xmx * fabs(q) / n);
-    int k = 0;
+    // a zero bound (every dy_c is 0: all pixels masked, gamma = 0, a zero dout channel) takes
+    // the top of the clamp as dy_scale_kernel does: dy2_c stays 0, and W[c] / scale[c] cannot
+    // set the fp16 range of the data gradient's packed columns
+    int k = bound == 0.0 ? 126 : 0;
     if (bound > 0.0 && isfinite(bound)) {
         int ex = 0;
         frexp(bound, &ex);   // bound in [2^(ex-1), 2^ex)
@@ -499,7 +515,7 @@ __global__ __launch_bounds__(kB) void bn_bwd_partial_sc2_kernel(
             const float xh = (v.v[e] - mu[e]) * is[e];
             const float gg = bwd_g<LA, MASKY>(d.v[e], MASKY ? 0.f : o.v[e], xh, gm[e], bt[e]);
             s[e] += (double)gg;
-            q[e] += (double)gg * (double)xh;
+            q[e] += (double)gg * xhat64(v.v[e], mu[e], is[e]);
             mg[e] = fmaxf(mg[e], fabsf(gg));
             mx[e] = fmaxf(mx[e], fabsf(xh));
         }
@@ -1204,13 +1220,18 @@ __global__ __launch_bounds__(kB) void dy_to_s2_kernel(const uint8_t* __restrict_
     s2::store_g8(out + i * 32, v);
 }
 
-// scale[c] = 2^k with amax[c] 2^k in [2^14, 2^15) (1 for an all-zero or non-finite channel)
+// scale[c] = 2^k with amax[c] 2^k in [2^14, 2^15), k clamped to [-126, 126] (1 for a
+// non-finite channel).  An all-zero channel takes the top of the clamp, 2^126, the limit of
+// ever smaller gradients: its dy2 and dW stay exactly 0, and in the data gradient's operand
+// W[c] / scale[c] its weights vanish — with scale 1 they would be the largest entries of
+// every packed column and set its fp16 range, pushing the live channels' entries (W / 2^30
+// and below) into fp16's subnormals.
 __global__ __launch_bounds__(kB) void dy_scale_kernel(const uint32_t* __restrict__ amax,
                                                       float* __restrict__ scale, int n) {
     const int i = blockIdx.x * kB + threadIdx.x;
     if (i >= n) return;
     const float a = __uint_as_float(amax[i]);
-    int k = 0;
+    int k = a == 0.f ? 126 : 0;
     if (a > 0.f && isfinite(a)) {
         int ex = 0;
         frexpf(a, &ex);   // a in [2^(ex-1), 2^ex)
@@ -1362,7 +1383,9 @@ __global__ __launch_bounds__(kB) void pack_f16_scale_kernel(const float* __restr
         if (t > 0.f && isfinite(t)) {
             int ex = 0;
             frexpf(t, &ex);              // t in [2^(ex-1), 2^ex)
-            sc = ldexpf(1.f, ex - 1 - 14);
+            // (kept a normal float: a column of nothing but weights over the 2^126 of
+            // gradient-free dy channels must not get a scale that underflows to 0)
+            sc = ldexpf(1.f, max(ex - 1 - 14, -126));
         }
         wscale[m] = sc;
     }
@@ -1431,7 +1454,7 @@ __global__ __launch_bounds__(kB) void pack_multi_scale_kernel(const PackDesc* __
         if (v > 0.f && isfinite(v)) {
             int ex = 0;
             frexpf(v, &ex);
-            sc = ldexpf(1.f, ex - 1 - 14);
+            sc = ldexpf(1.f, max(ex - 1 - 14, -126));
         }
         d.wscale[m] = sc;
     }
@@ -2013,7 +2036,7 @@ extern "C" int tcam_bn_relu_bwd_s3s2(const void* dout, const void* out, const vo
 }
 
 // dy (S3, P pixels x C channels) -> scale[c] (the power of two with amax[c] scale in
-// [2^14, 2^15), 1 for an all-zero channel) and dy2, its scaled S2 copy.  amax from
+// [2^14, 2^15); 2^126 for an all-zero channel) and dy2, its scaled S2 copy.  amax from
 // tcam_bn_relu_bwd_s3s2, or computed here when `compute` is set (amax zeroed first).
 extern "C" int tcam_dy_scaled_s2(const void* dy, long P, int C, uint32_t* amax, int compute,
                                  float* scale, void* dy2, void* stream) {

@@ -108,27 +108,34 @@ def test_wgrad11_amp_matches_fp64(cuda, B, cin, cout, H, W, stride):
 
 @pytest.mark.parametrize("H,W", [(14, 14), (13, 11), (112, 112)])
 def test_maxpool_bwd_matches_torch(cuda, H, W):
-    """MaxPool2d(3, 2, 1) backward (S3 gradient, S2 forward input) == torch's autograd on the
-    same values, including ties (values on a 0.5 grid, ReLU zeros): the first maximum in
-    (kh, kw) scan order takes the gradient."""
+    """MaxPool2d(3, 2, 1) backward (S3 gradient, S2 forward input; then the AMP form, S1 both)
+    == torch's autograd on the same values, including ties (values on a 0.5 grid, ReLU zeros):
+    the first maximum in (kh, kw) scan order takes the gradient.  AMP stores the sum (of up to
+    four window gradients) as fp16: half an fp16 ulp of the fp64 sum, 2^-25 below the normal
+    range."""
     g = torch.Generator().manual_seed(H * W)
     B, C = 2, 16
     x = (torch.randn(B, C, H, W, generator=g) * 2).round() / 2
     x = x.clamp(min=0)
-    xs = _act(x, cuda, "f16x3")
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     gout = torch.randn(B, C, Ho, Wo, generator=g)
-    gs = _act(gout, cuda, "x6")
     lib = _lib.load()
     ws = torch.empty(lib.tcam_maxpool_bwd_ws_bytes(B, C, Ho, Wo), dtype=torch.uint8,
                      device=cuda)
-    gin = ops.s3_empty(B, H, W, C, cuda)
-    assert lib.tcam_maxpool3x3s2_bwd_s3s2(gs.data_ptr(), xs.data_ptr(), gin.data_ptr(),
-                                          ws.data_ptr(), B, C, H, W, Ho, Wo, _st()) == 0
-    xr = _nchw(xs).requires_grad_(True)
-    F.max_pool2d(xr, 3, 2, 1).backward(_nchw(gs))
-    got = _nchw(gin)
-    assert torch.allclose(got, xr.grad, rtol=1e-6, atol=1e-7)
+    for amp in (False, True):
+        xs = _act(x, cuda, "amp" if amp else "f16x3")
+        gs = _act(gout, cuda, "amp" if amp else "x6")
+        gin = ops.lay_empty("s1" if amp else "s3", B, H, W, C, cuda)
+        fn = lib.tcam_maxpool3x3s2_bwd_s1 if amp else lib.tcam_maxpool3x3s2_bwd_s3s2
+        assert fn(gs.data_ptr(), xs.data_ptr(), gin.data_ptr(), ws.data_ptr(), B, C, H, W, Ho,
+                  Wo, _st()) == 0
+        xr = _nchw(xs).requires_grad_(True)
+        F.max_pool2d(xr, 3, 2, 1).backward(_nchw(gs))
+        got = _nchw(gin)
+        if amp:
+            assert ((got - xr.grad).abs() <= 2.0 ** -11 * xr.grad.abs() + 2.0 ** -25).all()
+        else:
+            assert torch.allclose(got, xr.grad, rtol=1e-6, atol=1e-7)
 
 
 @pytest.mark.parametrize("fmt", ["f16x3", "amp"])
@@ -199,6 +206,16 @@ def test_grad_add_mask_and_zero_up2_exact(cuda):
                                        r.data_ptr(), B * H * W, C, _st()) == 0
     ref = (a + torch.where(_nchw(os_).float() > 0, d, torch.zeros_like(d))).double()
     assert torch.equal(_nchw(r), ref)
+    # AMP (_s1): fp16 a, d, o; the sum stored as fp16 (autocast's gradient accumulation):
+    # half an fp16 ulp of the fp64 sum (plus fp32's own rounding of it)
+    a1, d1, o1 = _act(a, cuda, "amp"), _act(d, cuda, "amp"), _act(o, cuda, "amp")
+    r1 = torch.empty_like(a1)
+    assert lib.tcam_grad_add_mask_s1(a1.data_ptr(), d1.data_ptr(), o1.data_ptr(), r1.data_ptr(),
+                                     B * H * W, C, _st()) == 0
+    ref1 = _nchw(a1) + torch.where(_nchw(o1) > 0, _nchw(d1), torch.zeros_like(_nchw(d1)))
+    assert ((_nchw(r1) - ref1).abs() <= (2.0 ** -11 + 2.0 ** -24) * ref1.abs() + 2.0 ** -25).all()
+    masked = _nchw(o1) == 0
+    assert masked.any() and torch.equal(_nchw(r1)[masked], _nchw(a1)[masked])
     for fmt, gb in (("f16x3", 32), ("amp", 16), ("x6", 48)):
         src = _act(torch.randn(B, C, 5, 6, generator=g), cuda, fmt)
         out = ops.act_empty(src, B, H, W, C)

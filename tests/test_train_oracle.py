@@ -10,6 +10,7 @@ import torch
 
 from oracle import crf_ref
 from oracle import train_ref as T
+from sgd_ref import LR, SGD_CFGS, f32, sgd_ref
 
 G = os.path.join(os.path.dirname(__file__), "golden", "tcam_losses.npz")
 CASES = ("a", "b", "c")
@@ -125,3 +126,22 @@ def test_stdcl_step_oracle_matches_reference_goldens(case):
         np.testing.assert_allclose(bufs[k + ".running_var"].numpy(), g["rv/" + k], rtol=2e-5)
     feat, cls = T.stdcl_param_groups(names)
     assert [len(feat), len(cls)] == list(g["group_sizes"])
+
+
+def test_sgd_restatement_equals_torch_optim_sgd():
+    """The fp64 restatement the kernels are checked against == torch.optim.SGD
+    over three steps, every configuration."""
+    for cfg in SGD_CFGS:
+        m, damp, wd, nest, gs = cfg
+        g0 = torch.Generator().manual_seed(1)
+        p = torch.randn(50, generator=g0, dtype=torch.float64)
+        q = p.clone().requires_grad_(True)
+        opt = torch.optim.SGD([q], lr=f32(LR), momentum=f32(m), dampening=f32(damp),
+                              weight_decay=f32(wd), nesterov=bool(nest))
+        buf = torch.zeros_like(p)
+        for step in range(3):
+            g = torch.randn(50, generator=g0, dtype=torch.float64)
+            q.grad = g * f32(gs)
+            opt.step()
+            p, buf, _, _ = sgd_ref(p, g, buf, step == 0, cfg)
+            assert torch.allclose(p, q.detach(), rtol=1e-14, atol=1e-15), cfg
