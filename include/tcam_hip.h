@@ -825,6 +825,36 @@ int tcam_cls_bwd(const float* dlogits, const float* pooled, const float* w, int 
 int tcam_pool_bwd_s3(const float* dpooled, int B, long HW, int C, void* dout, void* stream);
 int tcam_pool_bwd_s1(const float* dpooled, int B, long HW, int C, void* dout, void* stream);
 
+/* ------------------------------- VGG16 classifier training step (csrc/vgg_train.hip) */
+/* Stage 1 with --encoder_name vgg16 (encoders/vgg.py:61-161: conv3x3 + bias + ReLU, no
+ * BatchNorm, MaxPool2d(2, 2), conv6 512 -> 1024).  Forward, head, data / weight gradients and
+ * the optimiser are the entries above; these are the two adjoints a BatchNorm-less stack adds.
+ * Suffixes as above: _s3s2 gradients S3 and activations S2, _s1 the AMP step's fp16 tensors.
+ * Every entry checks its geometry (C a multiple of 8, non-null distinct pointers, workspace
+ * bytes, Ho = H / 2 and Wo = W / 2 with floor) and returns TCAM_E_ARG instead of launching.
+ * Their index arithmetic is csrc/vgg_train_addr.h (checked on the host over whole grids). */
+/* ReLU backward with the bias gradient: dz (P, C) = dout [out > 0], out the saved post-ReLU
+ * activation (a copy or 0: exact); db[c] = sum_p dz[p, c], fp32 per thread and fp64 across
+ * threads and blocks in a fixed order (deterministic; _s1: rounded to fp16, an autocast
+ * conv's bias gradient); amax (C uint32, or NULL; zeroed here): the per-channel max |dz| as
+ * float bit patterns, what tcam_dy_scaled_s2(compute = 0) consumes — a channel with out <= 0
+ * everywhere gives dz = 0, db = 0, amax = 0 and so scale 2^126.  C <= 2048.
+ * ws: tcam_relu_bwd_ws_bytes(P, C) bytes (0 = unsupported geometry). */
+size_t tcam_relu_bwd_ws_bytes(long P, int C);
+int tcam_relu_bwd_s3s2(const void* dout, const void* out, void* dz, float* db, uint32_t* amax,
+                       long P, int C, void* ws, size_t ws_bytes, void* stream);
+int tcam_relu_bwd_s1(const void* dout, const void* out, void* dz, float* db, uint32_t* amax,
+                     long P, int C, void* ws, size_t ws_bytes, void* stream);
+/* MaxPool2d(2, 2) backward (encoders/vgg.py:146-161): gin (B, H, W, C) from gout
+ * (B, H / 2, W / 2, C); each window's gradient goes to its first maximum in (kh, kw) order,
+ * NaN wins (torch's max_pool2d rule, as tcam_maxpool3x3s2_bwd_*), recomputed from the forward
+ * input x (B, H, W, C).  The windows do not overlap: one thread writes all four pixels of a
+ * window, no atomics, no workspace.  A last odd row / column gets zero. */
+int tcam_maxpool2x2_bwd_s3s2(const void* gout, const void* x, void* gin, int B, int C, int H,
+                             int W, int Ho, int Wo, void* stream);
+int tcam_maxpool2x2_bwd_s1(const void* gout, const void* x, void* gin, int B, int C, int H, int W,
+                           int Ho, int Wo, void* stream);
+
 /* ------------------------------------------------------------- seeding */
 /*
  * TCAM pseudo-label seeds, batched: TCAMSeeder.forward (dlib/cams/tcam_seeding.py:187-258)

@@ -8,6 +8,10 @@ algorithmic FLOPs (conv forward + data gradient (no stem) + weight gradient, cou
 the model's geometry) against the MFMA ceiling of the precision.
 
     python scripts/bench_stdcl.py [--steps K] [--warmup W] [--batch 32] [--amp]
+                                  [--encoder_name {resnet50,vgg16}]
+
+``--encoder_name vgg16``: the same step of the VGG16 (WSOL16) classifier
+(vgg_training.VGG16ClassifierTrainer), FLOPs from its layer table.
     torchrun --nproc-per-node N scripts/bench_stdcl.py ...
 """
 import argparse
@@ -22,8 +26,8 @@ import torch.distributed as dist
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from tcam_wsol_video_amd.cl_training import ClassifierTrainer  # noqa: E402
-from tcam_wsol_video_amd.models import build_r50_stdcl  # noqa: E402
+from tcam_wsol_video_amd.cl_training import ClassifierTrainer, make_classifier_trainer  # noqa: E402
+from tcam_wsol_video_amd.models import build_r50_stdcl, build_stdcl  # noqa: E402
 
 PEAK_F16 = 2516.8          # TF/s dense fp16 MFMA (MI355X_MICROARCH)
 PEAK = {"f16x3": PEAK_F16 / 3, "amp": PEAK_F16}
@@ -57,13 +61,31 @@ def step_gflop(model, H: int, W: int) -> dict:
     return {"fwd": fwd, "dgrad": dgrad, "wgrad": fwd, "total": fwd + dgrad + fwd}
 
 
+def vgg_step_gflop(model, H: int, W: int) -> dict:
+    """The same for the VGG16 classifier, from its layer table (vgg_training.vgg_stack):
+    every conv3x3's forward at its resolution (a MaxPool2d(2, 2) halves it, floor), the data
+    gradient of all but the first conv, the weight gradient of all."""
+    from tcam_wsol_video_amd.vgg_training import vgg_stack
+    fwd = dgrad = 0.0
+    for i, c in enumerate(vgg_stack(model)):
+        fl = 2.0 * c.cout * c.cin * 9 * H * W / 1e9
+        fwd += fl
+        if i:
+            dgrad += fl
+        if c.pool:
+            H, W = H // 2, W // 2
+    return {"fwd": fwd, "dgrad": dgrad, "wgrad": fwd, "total": fwd + dgrad + fwd}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--amp", action="store_true")
+    ap.add_argument("--encoder_name", default="resnet50", choices=("resnet50", "vgg16"))
     args = ap.parse_args()
+    vgg = args.encoder_name == "vgg16"
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -72,13 +94,15 @@ def main():
         torch.cuda.set_device(local)
         dist.init_process_group("nccl", rank=rank, world_size=world)
     dev = torch.device("cuda", local)
-    model = build_r50_stdcl(seed=0)
-    gf = step_gflop(model, 224, 224)
+    model = build_stdcl("vgg16", seed=0) if vgg else build_r50_stdcl(seed=0)
+    gf = vgg_step_gflop(model, 224, 224) if vgg else step_gflop(model, 224, 224)
     model = model.to(dev)
     x, _, _ = bench.make_clip(args.batch, seed=3000 + rank)
     y = (torch.arange(args.batch) * 7 + rank) % 10
     xd, yd = x.to(dev), y.to(dev)
-    tr = ClassifierTrainer(model, lr=0.001, amp=args.amp)
+    tr = make_classifier_trainer(model, lr=0.001, amp=args.amp) if vgg else \
+        ClassifierTrainer(model, lr=0.001, amp=args.amp)
+    nparam = tr.flat.numel() / 1e6
     for _ in range(args.warmup):
         tr.step(xd, yd)
     torch.cuda.synchronize()
@@ -103,7 +127,8 @@ def main():
     ach = fps * gf["total"] / 1e3
     if rank == 0:
         print(json.dumps({
-            "metric": "frames/sec stage-1 STD_CL training step, ResNet50 WSOL 224x224",
+            "metric": "frames/sec stage-1 STD_CL training step, %s WSOL 224x224" %
+                      ("VGG16" if vgg else "ResNet50"),
             "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2),
             "frames_per_step_per_gpu": args.batch, "scaling": "weak", "train_prec": prec,
@@ -118,7 +143,7 @@ def main():
             "applied_steps": tr.applied_steps, "skipped_steps": tr.skipped_steps,
             "loss_last": round(float(loss), 5),
             "data": "synthetic frames/labels, random-init weights",
-            "parallelism": f"ddp{world} (RCCL all-reduce of the 23.5M fp32 gradient)"}),
+            "parallelism": f"ddp{world} (RCCL all-reduce of the {nparam:.1f}M fp32 gradient)"}),
             flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -243,6 +243,12 @@ SIGNATURES = {
     "tcam_cls_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "tcam_pool_bwd_s3": (_I, [_P, _I, C.c_long, _I, _P, _P]),
     "tcam_pool_bwd_s1": (_I, [_P, _I, C.c_long, _I, _P, _P]),
+    # VGG16 classifier training step (csrc/vgg_train.hip)
+    "tcam_relu_bwd_ws_bytes": (C.c_size_t, [C.c_long, _I]),
+    "tcam_relu_bwd_s3s2": (_I, [_P, _P, _P, _P, _P, C.c_long, _I, _P, C.c_size_t, _P]),
+    "tcam_relu_bwd_s1": (_I, [_P, _P, _P, _P, _P, C.c_long, _I, _P, C.c_size_t, _P]),
+    "tcam_maxpool2x2_bwd_s3s2": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "tcam_maxpool2x2_bwd_s1": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "bilateralfilter_batch": (None, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _F, _F]),
     "colorbilateralfilter_batch": (None, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I]),
 }

@@ -819,6 +819,24 @@ def train_forward(model: STDClassifier, images: torch.Tensor) -> torch.Tensor:
     return logits
 
 
+def classifier_trainer_class(encoder_name: str):
+    """The stage-1 trainer class of an encoder (no device is touched): ResNet50 ->
+    :class:`ClassifierTrainer`, VGG16 -> :class:`~.vgg_training.VGG16ClassifierTrainer`."""
+    if encoder_name == RESNET50:
+        return ClassifierTrainer
+    if encoder_name == "vgg16":
+        from .vgg_training import VGG16ClassifierTrainer
+        return VGG16ClassifierTrainer
+    raise NotImplementedError(f"stage-1 training runs the ResNet50 and VGG16 encoders, not "
+                              f"{encoder_name!r} (InceptionV3 stage 1 is not built)")
+
+
+def make_classifier_trainer(model: STDClassifier, **kw):
+    """The stage-1 trainer of ``model``, chosen by its ``encoder_name``; ``kw`` are
+    :class:`ClassifierTrainer`'s constructor arguments (both classes take the same)."""
+    return classifier_trainer_class(getattr(model, "encoder_name", None))(model, **kw)
+
+
 class _ClStepLR:
     """MyStepLR (learning/lr_scheduler.py:6-35) over the reference's two SGD groups
     (instantiators.py:806-807): each group's rate is max(base_g * gamma ** (epoch //

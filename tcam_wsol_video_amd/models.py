@@ -722,6 +722,11 @@ class STDClassifier(nn.Module, _HipModelMixin):
             from .cl_training import train_forward
             self.features = self.features_exp = None
             return train_forward(self, x)
+        if self.training and self.encoder_name == "vgg16":
+            # the same for the VGG16 classifier (no BatchNorm: conv + bias + ReLU, 2x2 pools)
+            from .vgg_training import train_forward
+            self.features = self.features_exp = None
+            return train_forward(self, x)
         head = self.classification_head
         fw, fb = head.fc.weight.detach().contiguous(), head.fc.bias.detach().contiguous()
         prec = _precision(self)

@@ -774,25 +774,27 @@ def train_stdcl_main(args) -> int:
     autocast), validated with the STD_CL CAM (inference_wsol.py, model selection best_loc /
     best_cl), checkpointed as the reference does; its best_loc / best_cl folders are what
     TCAM's ``--pretrained_classifier`` loads (README.md:267-276)."""
-    from .cl_training import ClassifierTrainer, lr_schedule as lr_schedule_cl
+    from .cl_training import make_classifier_trainer, lr_schedule as lr_schedule_cl
     from .training import fill_minibatch
     if args.freeze_cl:
         raise SystemExit("STD_CL trains the classifier: --freeze_cl False (parseit.py:873-875)")
     if args.freeze_encoder:
         raise SystemExit("--freeze_encoder True is a C_BOX switch (config.py:236-238); stage 1 "
                          "trains the encoder")
-    if args.encoder_name != "resnet50":
-        raise SystemExit("stage-1 training runs the ResNet50 encoder (README.md:239-266)")
+    if args.encoder_name not in ("resnet50", "vgg16"):
+        raise SystemExit(f"stage-1 training runs the ResNet50 and VGG16 encoders; "
+                         f"--encoder_name {args.encoder_name} (InceptionV3 stage 1) is not built")
     dev = _init_dist(args)
     rank, world = rank_world()
     model = create_model(**_model_kwargs(args))
     from .utils.seeding import seed_module_
     seed_module_(model, args.seed)
     model = model.to(dev)
-    tr = ClassifierTrainer(model, lr=args.opt__lr, momentum=args.opt__momentum,
-                           dampening=args.opt__dampening, weight_decay=args.opt__weight_decay,
-                           nesterov=args.opt__nesterov,
-                           lr_classifier_ratio=args.opt__lr_classifier_ratio, amp=args.amp)
+    tr = make_classifier_trainer(model, lr=args.opt__lr, momentum=args.opt__momentum,
+                                 dampening=args.opt__dampening,
+                                 weight_decay=args.opt__weight_decay,
+                                 nesterov=args.opt__nesterov,
+                                 lr_classifier_ratio=args.opt__lr_classifier_ratio, amp=args.amp)
     sched = (lr_schedule_cl(tr, args.opt__step_size, args.opt__gamma, args.opt__min_lr)
              if args.opt__lr_scheduler else None)
     save_dir = os.path.join(args.exp_path, "checkpoints")

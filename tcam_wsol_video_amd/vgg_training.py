@@ -1,0 +1,415 @@
+"""Stage-1 training of the VGG16 (WSOL16) ``STDClassifier`` on the gfx950 kernels: the
+reference's ``Trainer._wsol_training`` for task STD_CL with ``--encoder_name vgg16
+--freeze_encoder False`` (learning/train_wsol.py:700-714; encoders/vgg.py:61-161), the run
+whose best weights a VGG16-TCAM run starts from.
+
+Forward (train mode = the eval forward with every conv output kept): conv3x3 + bias + ReLU
+on the MFMA conv kernels (no BatchNorm), ``MaxPool2d(2, 2)``, ``conv6`` 512 -> 1024, WGAP's
+pool + fc.  Loss: ``nn.CrossEntropyLoss``.  Backward, per conv in reverse: the 2x2 max-pool
+adjoint where a pool follows (``tcam_maxpool2x2_bwd_*``), the ReLU backward with the bias
+gradient and the channel maxima (``tcam_relu_bwd_*``), the per-channel scaled S2 copy
+(``tcam_dy_scaled_s2``; a channel that is dead on the whole batch — there is no BatchNorm to
+revive it — gets scale 2^126, so its weight and bias gradients are exactly 0), the 3x3
+weight gradient (``tcam_conv_wgrad_s2_f16x3`` / ``_s1``) and, for every conv but the first,
+the data gradient as the forward conv of dy with the packed transposed weights.  Update:
+torch.optim.SGD with the reference's two VGG groups (process/instantiators.py:736-807:
+``encoder.features.*`` at ``lr``; ``encoder.conv6.*`` and ``classification_head.*`` at ``lr *
+lr_classifier_ratio``), gated on the device as the ResNet50 step is.
+
+Precision: ``prec="f16x3"`` (activations S2, gradients S3) or ``amp=True`` (S1 tensors, the
+device GradScaler), as :class:`~.cl_training.ClassifierTrainer`, whose public surface this
+class has, so checkpoints, the lr schedule and the runner work on either.
+
+Every launch goes to the current stream (no side stream).  Every scratch buffer belongs to
+one kernel and one geometry, is sized by that kernel's own ``*_ws_bytes`` query and is never
+regrown or shared between differently shaped calls.
+"""
+from __future__ import annotations
+
+import os
+from typing import Dict, List, Optional, Tuple
+
+import torch
+import torch.distributed as dist
+import torch.nn as nn
+
+from . import _lib, ops
+from ._lib import check, tcam_conv_src
+from .cl_training import ENCODER_PLANS, ClassifierTrainer, _TrainForwardCl, _p, _stream
+from .models import STDClassifier
+from .ops import ConvSrc
+
+VGG16 = "vgg16"
+
+
+class _VConv:
+    """One conv3x3 (pad 1, with bias) + ReLU of the stack, ``pool``: a MaxPool2d(2, 2)
+    follows; ``wt`` / ``wsc`` the forward's packed operand, ``dwt`` / ``dsc`` the data
+    gradient's, ``cin_pad``: the input's stored channels (8 for the image)."""
+
+    __slots__ = ("name", "conv", "cout", "cin", "cin_pad", "pool", "wt", "wsc", "dwt", "dsc",
+                 "bias16", "dw_pad")
+
+    def __init__(self, name: str, conv: nn.Conv2d):
+        self.name, self.conv = name, conv
+        self.cout, self.cin = conv.out_channels, conv.in_channels
+        self.cin_pad = (self.cin + 7) // 8 * 8
+        self.pool = False
+        self.wt = self.wsc = self.dwt = self.dsc = self.bias16 = self.dw_pad = None
+
+
+def _is_conv3x3(m) -> bool:
+    return (isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3) and m.stride == (1, 1) and
+            m.padding == (1, 1) and m.dilation == (1, 1) and m.groups == 1 and
+            m.bias is not None and m.out_channels % 8 == 0)
+
+
+def _is_pool2x2(m) -> bool:
+    def two(v):
+        return v == 2 or v == (2, 2)
+    return (isinstance(m, nn.MaxPool2d) and two(m.kernel_size) and two(m.stride) and
+            m.padding in (0, (0, 0)) and m.dilation in (1, (1, 1)) and not m.ceil_mode)
+
+
+def vgg_stack(model) -> List[_VConv]:
+    """The conv stack of a VGG16 ``STDClassifier`` in forward order (``encoder.features`` then
+    ``encoder.conv6``); raises when ``encoder.features`` is not the conv3x3-pad1 / ReLU /
+    MaxPool2d(2, 2) WSOL16 layout."""
+    enc = model.encoder
+    bad = NotImplementedError("VGG16 stage-1 training runs the WSOL16 stack: conv3x3 pad 1 + "
+                              "ReLU and MaxPool2d(2, 2) (encoders/vgg.py:146-161)")
+    mods = list(enc.features.named_children())
+    out: List[_VConv] = []
+    i = 0
+    while i < len(mods):
+        k, m = mods[i]
+        if _is_conv3x3(m):
+            if i + 1 >= len(mods) or not isinstance(mods[i + 1][1], nn.ReLU):
+                raise bad
+            if m.in_channels != (out[-1].cout if out else 3):
+                raise bad
+            out.append(_VConv(f"encoder.features.{k}", m))
+            i += 2
+        elif _is_pool2x2(m) and out and not out[-1].pool:
+            out[-1].pool = True
+            i += 1
+        else:
+            raise bad
+    conv6 = getattr(enc, "conv6", None)
+    if not out or not _is_conv3x3(conv6) or conv6.in_channels != out[-1].cout:
+        raise bad
+    out.append(_VConv("encoder.conv6", conv6))
+    return out
+
+
+class VGG16ClassifierTrainer:
+    """Trains every parameter of a VGG16 ``STDClassifier`` (encoder + WGAP head)."""
+
+    def __init__(self, model: STDClassifier, lr: float = 0.001, momentum: float = 0.9,
+                 dampening: float = 0.0, weight_decay: float = 1e-4, nesterov: bool = True,
+                 lr_classifier_ratio: float = 10.0, cl_lambda: float = 1.0, amp: bool = False,
+                 init_scale: float = 2.0 ** 16, growth_factor: float = 2.0,
+                 backoff_factor: float = 0.5, growth_interval: int = 2000,
+                 prec: Optional[str] = None):
+        if getattr(model, "encoder_name", None) != VGG16:
+            raise NotImplementedError("VGG16ClassifierTrainer trains the VGG16 STDClassifier")
+        self.model = model
+        self.dev = next(model.parameters()).device
+        if self.dev.type != "cuda":
+            raise RuntimeError("training runs on the MI355X HIP path only")
+        self.momentum, self.dampening = momentum, dampening
+        self.weight_decay, self.nesterov = weight_decay, nesterov
+        self.lr_ratio = float(lr_classifier_ratio)
+        self.lrs = [float(lr), float(lr) * self.lr_ratio]   # the two parameter groups
+        self.cl_lambda = float(cl_lambda)
+        self.amp = bool(amp)
+        prec = prec or os.environ.get("TCAM_TRAIN_PREC", "f16x3")
+        if not self.amp and prec != "f16x3":
+            raise ValueError(f"stage-1 training precision {prec!r}: 'f16x3' (or amp=True)")
+        self.fmt = "amp" if self.amp else "f16x3"
+        self.lay = ops.FMT_LAYOUT[self.fmt]      # activations: S1 / S2
+        self.glay = "s1" if self.amp else "s3"   # gradients: S1 / S3
+        self.scaler_cfg = (float(growth_factor), float(backoff_factor), int(growth_interval))
+        self.convs = vgg_stack(model)
+        self.fc: nn.Linear = model.classification_head.fc
+        # flat parameter / gradient / momentum buffers (named_parameters order:
+        # encoder.features.*, then encoder.conv6.* and the head — the reference's second
+        # group, at lr * lr_classifier_ratio, is the tail; encoder.full_features.* are the
+        # same Parameters under a second name, which named_parameters lists once)
+        named = list(model.named_parameters())
+        self.params: List[nn.Parameter] = [p for _, p in named]
+        n = sum(p.numel() for p in self.params)
+        self.split, tail = 0, False
+        for name, p in named:
+            if name.startswith("encoder.features."):
+                if tail:
+                    raise NotImplementedError("encoder.features.* must precede conv6 / the head")
+                self.split += p.numel()
+            else:
+                tail = True
+        self.flat = torch.empty(n, device=self.dev, dtype=torch.float32)
+        # gradient + the step's loss (+ AMP's found_inf): all-reduced together
+        self._gbuf = torch.zeros(n + (2 if self.amp else 1), device=self.dev,
+                                 dtype=torch.float32)
+        self.grad = self._gbuf[:n]
+        self.loss_gate = self._gbuf[n:n + 1]
+        self.found_inf = self._gbuf[n + 1:n + 2] if self.amp else None
+        self.scale = torch.full((1,), float(init_scale), device=self.dev, dtype=torch.float32)
+        self.growth_tracker = torch.zeros(1, device=self.dev, dtype=torch.int32)
+        # the first group's scaler.update() writes a shadow (one update per step)
+        self._scale_shadow = self.scale.clone()
+        self._tracker_shadow = self.growth_tracker.clone()
+        self.mom = torch.zeros(n, device=self.dev, dtype=torch.float32)
+        # device counters per group: [applied steps, skipped steps]
+        self.step_counts = torch.zeros(2, device=self.dev, dtype=torch.int32)
+        self._counts_g1 = torch.zeros(2, device=self.dev, dtype=torch.int32)
+        self.views: Dict[int, torch.Tensor] = {}
+        off = 0
+        for p in self.params:
+            k = p.numel()
+            self.flat[off:off + k].copy_(p.detach().reshape(-1))
+            p.data = self.flat[off:off + k].view(p.shape)
+            self.views[id(p)] = self.grad[off:off + k].view(p.shape)
+            off += k
+        # the Parameters now live in the flat buffer: an eval plan folded from the old
+        # storage (keyed on data_ptr / _version only) must not survive
+        model.invalidate_plans(ENCODER_PLANS)
+        self.zero_bias: Dict[int, torch.Tensor] = {}
+        self.steps = 0
+        # scratch: one buffer per (kernel, geometry), sized by the kernel's own query
+        self._ws: Dict[Tuple, torch.Tensor] = {}
+        self.repack()
+
+    # ------------------------------------------------------------ helpers
+    # (ClassifierTrainer's, unchanged: they touch only attributes both trainers have)
+    lr = ClassifierTrainer.lr
+    trainable_names = ClassifierTrainer.trainable_names
+    loss_t = ClassifierTrainer.loss_t
+    close = ClassifierTrainer.close
+    g = ClassifierTrainer.g
+    _zeros = ClassifierTrainer._zeros
+    views_intact = ClassifierTrainer.views_intact
+    param_version = ClassifierTrainer.param_version
+    _pack = ClassifierTrainer._pack
+    loss_and_grad = ClassifierTrainer.loss_and_grad
+    step = ClassifierTrainer.step
+    check_overflow = ClassifierTrainer.check_overflow
+    applied_steps = ClassifierTrainer.applied_steps
+    skipped_steps = ClassifierTrainer.skipped_steps
+
+    def _scratch(self, kernel: str, geom: Tuple, nbytes: int) -> torch.Tensor:
+        """The scratch buffer of ``kernel`` at ``geom``: exactly ``nbytes`` (its own size
+        query's answer for that geometry), allocated once."""
+        nbytes = int(nbytes)
+        if nbytes <= 0:
+            raise ValueError(f"{kernel}: unsupported geometry {geom}")
+        key = (kernel,) + tuple(geom)
+        cur = self._ws.get(key)
+        if cur is None:
+            cur = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+            self._ws[key] = cur
+        elif cur.numel() != nbytes:
+            raise RuntimeError(f"{kernel}{geom}: workspace query changed "
+                               f"({cur.numel()} -> {nbytes} bytes)")
+        return cur
+
+    def repack(self):
+        """The forward operands of every conv from the flat fp32 weights (AMP: and the
+        fp16-rounded biases autocast gives a conv)."""
+        self._packed_version = self.param_version()
+        for c in self.convs:
+            c.wt, c.wsc = self._pack(c.conv.weight.data, 0, cin_pad=c.cin_pad,
+                                     out=(c.wt, c.wsc))
+            if self.amp:
+                if c.bias16 is None:
+                    c.bias16 = torch.empty(c.cout, device=self.dev, dtype=torch.float32)
+                c.bias16.copy_(c.conv.bias.data.half())
+
+    # ------------------------------------------------------------ forward
+    def forward(self, images: torch.Tensor):
+        """Train-mode forward: (cl_logits (B, K) fp32, state for :meth:`backward`)."""
+        lib = _lib.load()
+        if images.dim() != 4 or images.shape[1] != 3 or not images.is_cuda:
+            raise ValueError("expected a (B, 3, H, W) cuda tensor")
+        if self.param_version() != self._packed_version:
+            self.repack()
+        x = images.contiguous().float()
+        f = ops.s3_from_nchw(x, 8, self.fmt)
+        saved = []
+        for c in self.convs:
+            _, H, W, _ = ops.s3_dims(f)
+            bias = c.bias16 if self.amp else c.conv.bias.data
+            a = ops.conv2d_x6([ConvSrc(f)], c.wt, bias, c.cout, H, W, 3, 1, True, wscale=c.wsc)
+            saved.append((f, a))
+            if c.pool:
+                if H < 2 or W < 2:
+                    raise ValueError("input too small for the VGG16 pools")
+                f = ops.pool2d_s3(a, 2, 2, 0, "max")
+            else:
+                f = a
+        B, Hf, Wf, Cf = ops.s3_dims(f)
+        K = self.fc.out_features
+        pooled = torch.empty((B, Cf), device=self.dev, dtype=torch.float32)
+        logits = torch.empty((B, K), device=self.dev, dtype=torch.float32)
+        ws = self._scratch("cls_pool", (B, Cf), lib.tcam_cls_pool_ws_bytes(B, Cf))
+        check(getattr(lib, f"tcam_cls_fwd_{self.lay}")(
+            f.data_ptr(), B, Hf * Wf, Cf, self.fc.weight.data_ptr(), self.fc.bias.data_ptr(), K,
+            pooled.data_ptr(), logits.data_ptr(), ws.data_ptr(), _stream()),
+            f"tcam_cls_fwd_{self.lay}")
+        self.model.x_in = images
+        return logits, {"convs": saved, "pooled": pooled, "feat": f}
+
+    # ----------------------------------------------------------- backward
+    def _relu_bwd(self, dout: torch.Tensor, a: torch.Tensor, db: torch.Tensor):
+        """(dz, dy2, scale) of one conv's ReLU: dz = dout [a > 0] (S3 / S1), the bias gradient
+        into ``db``; f16x3: dy2 / scale the per-channel scaled S2 copy (AMP: None)."""
+        lib = _lib.load()
+        B, H, W, Cc = ops.s3_dims(a)
+        P = B * H * W
+        ws = self._scratch("relu_bwd", (P, Cc), lib.tcam_relu_bwd_ws_bytes(P, Cc))
+        dz = ops.lay_empty(self.glay, B, H, W, Cc, self.dev)
+        amax = None if self.amp else torch.empty(Cc, device=self.dev, dtype=torch.int32)
+        name = "tcam_relu_bwd_s1" if self.amp else "tcam_relu_bwd_s3s2"
+        check(getattr(lib, name)(dout.data_ptr(), a.data_ptr(), dz.data_ptr(), db.data_ptr(),
+                                 _p(amax), P, Cc, ws.data_ptr(), ws.numel(), _stream()), name)
+        if self.amp:
+            return dz, None, None
+        scale = torch.empty(Cc, device=self.dev, dtype=torch.float32)
+        dy2 = ops.lay_empty("s2", B, H, W, Cc, self.dev)
+        check(lib.tcam_dy_scaled_s2(dz.data_ptr(), P, Cc, amax.data_ptr(), 0, scale.data_ptr(),
+                                    dy2.data_ptr(), _stream()), "tcam_dy_scaled_s2")
+        return dz, dy2, scale
+
+    def _pool_bwd(self, gout: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
+        lib = _lib.load()
+        B, H, W, Cc = ops.s3_dims(a)
+        _, Ho, Wo, _ = ops.s3_dims(gout)
+        gin = ops.lay_empty(self.glay, B, H, W, Cc, self.dev)
+        name = "tcam_maxpool2x2_bwd_s1" if self.amp else "tcam_maxpool2x2_bwd_s3s2"
+        check(getattr(lib, name)(gout.data_ptr(), a.data_ptr(), gin.data_ptr(), B, Cc, H, W, Ho,
+                                 Wo, _stream()), name)
+        return gin
+
+    def _wgrad(self, c: _VConv, x: torch.Tensor, op: torch.Tensor,
+               scale: Optional[torch.Tensor]) -> None:
+        """The 3x3 weight gradient of ``c`` on input ``x`` from the MFMA copy of dy (``op``:
+        dy2 with its ``scale``, or AMP's S1 dz) into the flat gradient buffer."""
+        lib = _lib.load()
+        B, H, W, Cx = ops.s3_dims(x)
+        Cd = c.cout
+        arr = (tcam_conv_src * 1)()
+        arr[0] = tcam_conv_src(x.data_ptr(), Cx, H, W, 1, 0)
+        ws = self._scratch("conv_wgrad", (B, Cx, Cd, H, W),
+                           lib.tcam_conv_wgrad_ws_bytes(arr, 1, B, Cd, H, W, 3, 3))
+        gw = self.g(c.conv.weight)
+        dw = gw
+        if Cx != c.cin:   # the image padded to 8 channels: only the real ones are kept
+            if c.dw_pad is None:
+                c.dw_pad = torch.empty((Cd, Cx, 3, 3), device=self.dev, dtype=torch.float32)
+            dw = c.dw_pad
+        if self.amp:
+            check(lib.tcam_conv_wgrad_s1(arr, 1, B, op.data_ptr(), Cd, H, W, 3, 3, 1, 1, Cd,
+                                         dw.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+                  "tcam_conv_wgrad_s1")
+        else:
+            check(lib.tcam_conv_wgrad_s2_f16x3(arr, 1, B, op.data_ptr(), scale.data_ptr(), Cd, H,
+                                               W, 3, 3, 1, 1, Cd, dw.data_ptr(), ws.data_ptr(),
+                                               ws.numel(), _stream()),
+                  "tcam_conv_wgrad_s2_f16x3")
+        if dw is not gw:
+            gw.copy_(dw[:, :c.cin])
+
+    def _dgrad(self, c: _VConv, op: torch.Tensor, scale: Optional[torch.Tensor], H: int,
+               W: int) -> torch.Tensor:
+        """d loss / d (the input of ``c``): the stride-1 conv of dy's MFMA copy with the
+        transposed, rotated weight (divided by dy's scales on the f16x3 path)."""
+        c.dwt, c.dsc = self._pack(c.conv.weight.data, 1, sel=c.cin, kdiv=scale,
+                                  out=(c.dwt, c.dsc))
+        zero = self._zeros(c.cin)
+        if self.amp:
+            return ops.conv2d_x6([ConvSrc(op)], c.dwt, zero, c.cin, H, W, 3, 1, False)
+        return ops.conv2d_f16x3_s3out([ConvSrc(op)], c.dwt, c.dsc, zero, c.cin, H, W, 3, 1)
+
+    def backward(self, dlogits: torch.Tensor, st) -> None:
+        """Gradients of every parameter into the flat buffer from d loss / d logits."""
+        lib = _lib.load()
+        dlogits = dlogits.contiguous().float()
+        f = st["feat"]
+        B, Hf, Wf, Cf = ops.s3_dims(f)
+        K = self.fc.out_features
+        dpooled = torch.empty((B, Cf), device=self.dev, dtype=torch.float32)
+        check(lib.tcam_cls_bwd(dlogits.data_ptr(), st["pooled"].data_ptr(),
+                               self.fc.weight.data_ptr(), B, K, Cf, 1 if self.amp else 0,
+                               self.g(self.fc.weight).data_ptr(), self.g(self.fc.bias).data_ptr(),
+                               dpooled.data_ptr(), _stream()), "tcam_cls_bwd")
+        dout = ops.lay_empty(self.glay, B, Hf, Wf, Cf, self.dev)
+        check(getattr(lib, f"tcam_pool_bwd_{self.glay}")(dpooled.data_ptr(), B, Hf * Wf, Cf,
+                                                         dout.data_ptr(), _stream()),
+              f"tcam_pool_bwd_{self.glay}")
+        for i in range(len(self.convs) - 1, -1, -1):
+            c = self.convs[i]
+            x, a = st["convs"][i]
+            if c.pool:
+                dout = self._pool_bwd(dout, a)
+            dz, dy2, scale = self._relu_bwd(dout, a, self.g(c.conv.bias))
+            op = dz if self.amp else dy2
+            self._wgrad(c, x, op, scale)
+            if i == 0:
+                break   # the image needs no gradient
+            _, H, W, _ = ops.s3_dims(x)
+            dout = self._dgrad(c, op, scale, H, W)
+
+    # ------------------------------------------------------------- the step
+    def all_reduce_and_step(self) -> None:
+        """DDP average (RCCL all-reduce of the flat gradient + loss slot), the gated SGD step
+        of both parameter groups, repack; the model's eval plans are dropped (the kernels
+        write the weights without a version bump)."""
+        scale = 1.0
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(self._gbuf, op=dist.ReduceOp.SUM)
+            scale = 1.0 / dist.get_world_size()
+        lib = _lib.load()
+        n = self.flat.numel()
+        groups = ((0, self.split, self.lrs[0], self._counts_g1),
+                  (self.split, n, self.lrs[1], self.step_counts))
+        for gi, (a, e, lr, cnt) in enumerate(groups):
+            if e <= a:
+                continue
+            p, g, m = self.flat[a:e], self.grad[a:e], self.mom[a:e]
+            if self.amp:
+                gcfg = self.scaler_cfg
+                sc, tr = (self.scale, self.growth_tracker) if gi == 1 else \
+                    (self._scale_shadow, self._tracker_shadow)
+                check(lib.tcam_sgd_step_amp(p.data_ptr(), g.data_ptr(), m.data_ptr(), e - a, lr,
+                                            self.momentum, self.dampening, self.weight_decay,
+                                            1 if self.nesterov else 0, scale,
+                                            self._gbuf[-2:].data_ptr(), cnt.data_ptr(),
+                                            cnt.data_ptr() + 4, sc.data_ptr(), tr.data_ptr(),
+                                            gcfg[0], gcfg[1], gcfg[2], _stream()),
+                      "tcam_sgd_step_amp")
+            else:
+                check(lib.tcam_sgd_step_gated(p.data_ptr(), g.data_ptr(), m.data_ptr(), e - a, lr,
+                                              self.momentum, self.dampening, self.weight_decay,
+                                              1 if self.nesterov else 0, scale,
+                                              self.loss_gate.data_ptr(), cnt.data_ptr(),
+                                              cnt.data_ptr() + 4, _stream()),
+                      "tcam_sgd_step_gated")
+        self.repack()
+        self.model.invalidate_plans(ENCODER_PLANS)
+
+
+def train_forward(model: STDClassifier, images: torch.Tensor) -> torch.Tensor:
+    """cl_logits of a VGG16 STDClassifier in train mode, differentiable w.r.t. every
+    parameter when grad mode is on (one autograd node over the trainer's forward /
+    backward).  Used by STDClassifier.forward when ``model.training``."""
+    eng = model.__dict__.get("_train_engine")
+    amp = getattr(model, "conv_precision", None) == "amp"
+    if not isinstance(eng, VGG16ClassifierTrainer) or not eng.views_intact() or eng.amp != amp:
+        eng = VGG16ClassifierTrainer(model, amp=amp)
+        model.__dict__["_train_engine"] = eng
+    elif eng.param_version() != eng._packed_version:
+        eng.repack()
+    if torch.is_grad_enabled() and any(p.requires_grad for p in eng.params):
+        return _TrainForwardCl.apply(eng, images, *eng.params)
+    logits, _ = eng.forward(images)
+    return logits
