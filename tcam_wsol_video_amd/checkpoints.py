@@ -300,7 +300,7 @@ def save_checkpoint(trainer, save_dir: str, current_step: int, key: str = CHP_CP
 
 def _trainer_names(trainer) -> List[str]:
     """The parameter names of a trainer's flat buffer, in its order (DecoderTrainer: the
-    decoder + seg head; ClassifierTrainer: every model parameter)."""
+    decoder + seg head; a stage-1 trainer: every model parameter)."""
     if hasattr(trainer, "trainable_names"):
         return trainer.trainable_names()
     return trainable_names(trainer.model)
@@ -327,9 +327,7 @@ def load_checkpoint(trainer, save_dir: str, key: str = CHP_CP, lr_scheduler=None
             trainer.mom[off:off + k].copy_(mom[name].reshape(-1))
         off += k
     trainer.steps = 1 if mom else 0
-    for cnt in (trainer.step_counts, getattr(trainer, "_counts_g1", None)):
-        if cnt is None:
-            continue
+    for _, _, cnt in trainer._group_state:     # every parameter group's counters
         cnt.zero_()
         if mom:     # momentum present: the next step is not the optimizer's first
             cnt[0] = 1

@@ -33,20 +33,16 @@ import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
-import torch.distributed as dist
 import torch.nn as nn
 
 from . import _lib, ops
 from ._lib import check, tcam_conv_src, tcam_pack_item
+from .flat_sgd import FlatSGD, _stream
 from .models import RESNET50, STDClassifier
 from .ops import ConvSrc
 
 # STDClassifier's eval plans fold encoder weights / BN statistics
 ENCODER_PLANS = ("enc_x6", "enc_f16x3", "enc_amp", "enc")
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -81,8 +77,15 @@ class _Block:
             else None
 
 
-class ClassifierTrainer:
-    """Trains every parameter of a ResNet50 ``STDClassifier`` (encoder + WGAP head)."""
+class Stage1Trainer(FlatSGD):
+    """What the stage-1 trainers of every encoder share: the constructor arguments, the
+    precision and its formats, the weight packing, the WGAP head, ClLoss and the step.  A
+    subclass names its encoder (``ENCODER``), splits the parameters into the reference's two
+    SGD groups (:meth:`param_split`), builds its conv stack (:meth:`_build`) and has
+    ``repack``, ``forward`` and ``backward``."""
+
+    PLANS = ENCODER_PLANS
+    ENCODER = ""
 
     def __init__(self, model: STDClassifier, lr: float = 0.001, momentum: float = 0.9,
                  dampening: float = 0.0, weight_decay: float = 1e-4, nesterov: bool = True,
@@ -90,83 +93,33 @@ class ClassifierTrainer:
                  init_scale: float = 2.0 ** 16, growth_factor: float = 2.0,
                  backoff_factor: float = 0.5, growth_interval: int = 2000,
                  prec: Optional[str] = None):
-        if getattr(model, "encoder_name", None) != RESNET50:
-            raise NotImplementedError("stage-1 training runs the ResNet50 encoder "
-                                      "(README.md:239-266)")
+        if getattr(model, "encoder_name", None) != self.ENCODER:
+            raise NotImplementedError(f"{type(self).__name__} trains the {self.ENCODER} "
+                                      f"STDClassifier")
         self.model = model
-        self.dev = next(model.parameters()).device
-        if self.dev.type != "cuda":
+        if next(model.parameters()).device.type != "cuda":
             raise RuntimeError("training runs on the MI355X HIP path only")
         self.momentum, self.dampening = momentum, dampening
         self.weight_decay, self.nesterov = weight_decay, nesterov
         self.lr_ratio = float(lr_classifier_ratio)
         self.lrs = [float(lr), float(lr) * self.lr_ratio]   # the two parameter groups
         self.cl_lambda = float(cl_lambda)
-        self.amp = bool(amp)
         prec = prec or os.environ.get("TCAM_TRAIN_PREC", "f16x3")
-        if not self.amp and prec != "f16x3":
+        if not amp and prec != "f16x3":
             raise ValueError(f"stage-1 training precision {prec!r}: 'f16x3' (or amp=True)")
-        self.fmt = "amp" if self.amp else "f16x3"
-        self.lay = ops.FMT_LAYOUT[self.fmt]      # activations: S1 / S2
-        self.glay = "s1" if self.amp else "s3"   # gradients: S1 / S3
+        self.fmt = "amp" if amp else "f16x3"
+        self.lay = ops.FMT_LAYOUT[self.fmt]   # activations: S1 / S2
+        self.glay = "s1" if amp else "s3"     # gradients: S1 / S3
         self.scaler_cfg = (float(growth_factor), float(backoff_factor), int(growth_interval))
-        enc = model.encoder
-        self.stem = _EConv(enc.conv1, enc.bn1, cin_pad=8)
-        self.layers: List[List[_Block]] = [[_Block(b) for b in layer]
-                                           for layer in (enc.layer1, enc.layer2, enc.layer3,
-                                                         enc.layer4)]
         self.fc: nn.Linear = model.classification_head.fc
-        # flat parameter / gradient / momentum buffers (named_parameters order: the
-        # encoder, whose layer4 is last, then the head — so the reference's second
-        # parameter group, layer4 + head at lr * lr_classifier_ratio, is the tail)
-        named = list(model.named_parameters())
-        self.params: List[nn.Parameter] = [p for _, p in named]
-        n = sum(p.numel() for p in self.params)
-        self.split = 0
-        for name, p in named:
-            if name.startswith(("encoder.layer4.", "classification_head.")):
-                break
-            self.split += p.numel()
-        self.flat = torch.empty(n, device=self.dev, dtype=torch.float32)
-        # gradient + the step's loss (+ AMP's found_inf): all-reduced together
-        self._gbuf = torch.zeros(n + (2 if self.amp else 1), device=self.dev,
-                                 dtype=torch.float32)
-        self.grad = self._gbuf[:n]
-        self.loss_gate = self._gbuf[n:n + 1]
-        self.found_inf = self._gbuf[n + 1:n + 2] if self.amp else None
-        self.scale = torch.full((1,), float(init_scale), device=self.dev, dtype=torch.float32)
-        self.growth_tracker = torch.zeros(1, device=self.dev, dtype=torch.int32)
-        # the first group's scaler.update() writes a shadow (one update per step)
-        self._scale_shadow = self.scale.clone()
-        self._tracker_shadow = self.growth_tracker.clone()
-        self.mom = torch.zeros(n, device=self.dev, dtype=torch.float32)
-        # device counters per group: [applied steps, skipped steps]
-        self.step_counts = torch.zeros(2, device=self.dev, dtype=torch.int32)
-        self._counts_g1 = torch.zeros(2, device=self.dev, dtype=torch.int32)
-        self.views: Dict[int, torch.Tensor] = {}
-        off = 0
-        for p in self.params:
-            k = p.numel()
-            self.flat[off:off + k].copy_(p.detach().reshape(-1))
-            p.data = self.flat[off:off + k].view(p.shape)
-            self.views[id(p)] = self.grad[off:off + k].view(p.shape)
-            off += k
-        self.bns = [m for m in model.modules() if isinstance(m, nn.BatchNorm2d)]
-        self.zero_bias: Dict[int, torch.Tensor] = {}
-        self.steps = 0
-        self._ws: Dict[str, torch.Tensor] = {}
-        self.wgrad_side = os.environ.get("TCAM_WGRAD_SIDE", "1") != "0"
-        # the fused BN-ReLU backward with a bound-based MFMA scale (TCAM_FUSED_BN_BWD=0: the
-        # three-pass path: backward + channel maxima, scale, re-split)
-        self.fused_bn_bwd = os.environ.get("TCAM_FUSED_BN_BWD", "1") != "0"
-        # the stem's weight gradient as im2col + the 1x1 MFMA GEMM (0: the fp32-MFMA general path)
-        self.stem_im2col = os.environ.get("TCAM_STEM_IM2COL", "1") != "0"
-        # the repack as one batched launch (two on f16x3) once the operand buffers exist
-        self.batched_pack = os.environ.get("TCAM_BATCHED_PACK", "1") != "0"
-        self._pack_items = None
-        self._pack_table = None
-        self._wg_stream = None
-        self._stem_dw = None
+        self._build(model)
+        # every parameter, in named_parameters order; the reference's second group, at
+        # lr * lr_classifier_ratio, is the tail and carries the real scaler state
+        FlatSGD.__init__(self, list(model.parameters()), [self.param_split(model)], amp,
+                         init_scale)
+        # the Parameters now live in the flat buffer: an eval plan folded from the old
+        # storage (keyed on data_ptr / _version only) must not survive
+        model.invalidate_plans(ENCODER_PLANS)
         self.repack()
 
     # ------------------------------------------------------------ helpers
@@ -184,59 +137,6 @@ class ClassifierTrainer:
 
     def close(self) -> None:
         """(the trainer keeps nothing for the next step)"""
-
-    def g(self, p: torch.Tensor) -> torch.Tensor:
-        return self.views[id(p)]
-
-    def _zeros(self, n: int) -> torch.Tensor:
-        z = self.zero_bias.get(n)
-        if z is None:
-            z = torch.zeros(n, device=self.dev, dtype=torch.float32)
-            self.zero_bias[n] = z
-        return z
-
-    def _workspace(self, key: str, nbytes: int) -> torch.Tensor:
-        cur = self._ws.get(key)
-        if cur is None or cur.numel() < nbytes:
-            if cur is not None and self._wg_stream is not None:
-                cur.record_stream(self._wg_stream)
-            cur = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self.dev)
-            self._ws[key] = cur
-        return cur
-
-    def _convs(self):
-        yield self.stem
-        for layer in self.layers:
-            for b in layer:
-                yield b.c1
-                yield b.c2
-                yield b.c3
-                if b.ds is not None:
-                    yield b.ds
-
-    def views_intact(self) -> bool:
-        off, base = 0, self.flat.data_ptr()
-        for p in self.params:
-            if p.data_ptr() != base + 4 * off:
-                return False
-            off += p.numel()
-        return True
-
-    def param_version(self) -> int:
-        return sum(p._version for p in self.params)
-
-    @property
-    def bn_flat(self) -> torch.Tensor:
-        return torch.cat([t.reshape(-1) for bn in self.bns
-                          for t in (bn.running_mean, bn.running_var)])
-
-    def set_bn_flat(self, flat: torch.Tensor) -> None:
-        off = 0
-        for bn in self.bns:
-            for t in (bn.running_mean, bn.running_var):
-                k = t.numel()
-                t.copy_(flat[off:off + k].view_as(t))
-                off += k
 
     def _pack(self, w: torch.Tensor, mode: int, sel: int = 0, cin_pad: int = 0,
               kdiv: Optional[torch.Tensor] = None, out=None):
@@ -269,6 +169,149 @@ class ClassifierTrainer:
                                          ctot, kh, kw, 0, sel if mode else 0, cin_pad,
                                          _p(kdiv), _stream()), "tcam_pack_weight_f16x3")
         return wt, sc
+
+    def _images_s3(self, images: torch.Tensor) -> torch.Tensor:
+        """The batch as the first conv's input (8 stored channels), the operands repacked
+        first when an optimizer stepped the Parameters in place."""
+        if images.dim() != 4 or images.shape[1] != 3 or not images.is_cuda:
+            raise ValueError("expected a (B, 3, H, W) cuda tensor")
+        if self.param_version() != self._packed_version:
+            self.repack()
+        return ops.s3_from_nchw(images.contiguous().float(), 8, self.fmt)
+
+    # ---------------------------------------------------------- the WGAP head
+    def _head_fwd(self, f: torch.Tensor, ws: torch.Tensor):
+        """(cl_logits (B, K) fp32, pooled (B, C)) of the encoder output ``f``; ``ws``: the
+        caller's ``tcam_cls_pool_ws_bytes(B, C)`` workspace."""
+        B, Hf, Wf, Cf = ops.s3_dims(f)
+        K = self.fc.out_features
+        pooled = torch.empty((B, Cf), device=self.dev, dtype=torch.float32)
+        logits = torch.empty((B, K), device=self.dev, dtype=torch.float32)
+        check(getattr(_lib.load(), f"tcam_cls_fwd_{self.lay}")(
+            f.data_ptr(), B, Hf * Wf, Cf, self.fc.weight.data_ptr(), self.fc.bias.data_ptr(), K,
+            pooled.data_ptr(), logits.data_ptr(), ws.data_ptr(), _stream()),
+            f"tcam_cls_fwd_{self.lay}")
+        return logits, pooled
+
+    def _head_bwd(self, dlogits: torch.Tensor, f: torch.Tensor,
+                  pooled: torch.Tensor) -> torch.Tensor:
+        """The fc gradients into the flat buffer; returns d loss / d ``f`` (S3 / S1)."""
+        lib = _lib.load()
+        B, Hf, Wf, Cf = ops.s3_dims(f)
+        K = self.fc.out_features
+        dpooled = torch.empty((B, Cf), device=self.dev, dtype=torch.float32)
+        check(lib.tcam_cls_bwd(dlogits.data_ptr(), pooled.data_ptr(),
+                               self.fc.weight.data_ptr(), B, K, Cf, 1 if self.amp else 0,
+                               self.g(self.fc.weight).data_ptr(), self.g(self.fc.bias).data_ptr(),
+                               dpooled.data_ptr(), _stream()), "tcam_cls_bwd")
+        dout = ops.lay_empty(self.glay, B, Hf, Wf, Cf, self.dev)
+        check(getattr(lib, f"tcam_pool_bwd_{self.glay}")(dpooled.data_ptr(), B, Hf * Wf, Cf,
+                                                         dout.data_ptr(), _stream()),
+              f"tcam_pool_bwd_{self.glay}")
+        return dout
+
+    # ------------------------------------------------------------- the step
+    def loss_and_grad(self, logits: torch.Tensor, labels: torch.Tensor):
+        """ClLoss on the device: (loss (1,), d loss / d logits (times the AMP scale))."""
+        lab = labels.to(device=self.dev, dtype=torch.int32).contiguous()
+        B, K = logits.shape
+        loss = torch.empty(1, device=self.dev, dtype=torch.float32)
+        dl = torch.empty_like(logits)
+        check(_lib.load().tcam_ce_loss(logits.data_ptr(), lab.data_ptr(), B, K, self.cl_lambda,
+                                       _p(self.scale) if self.amp else None, loss.data_ptr(),
+                                       dl.data_ptr(), _stream()), "tcam_ce_loss")
+        return loss, dl
+
+    def step(self, images: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        """One optimisation step on a batch; returns the device loss (1,)."""
+        logits, st = self.forward(images)
+        loss, dl = self.loss_and_grad(logits, labels)
+        self.loss_gate.copy_(loss)
+        self.backward(dl, st)
+        if self.amp:   # scaler.unscale_: 1/scale, non-finite check (device)
+            self.found_inf.zero_()
+            check(_lib.load().tcam_amp_unscale(self.grad.data_ptr(), self.grad.numel(),
+                                               self.scale.data_ptr(),
+                                               self.found_inf.data_ptr(), _stream()),
+                  "tcam_amp_unscale")
+        else:
+            # an f16x3 operand beyond the fp16 range made this step invalid: skip it on the
+            # device on every rank (check_overflow() reports it)
+            self.loss_gate.masked_fill_(ops.f16_overflow_flag(self.dev).bool(), float("nan"))
+        self.all_reduce_and_step()
+        self.steps += 1
+        self.last_logits = logits
+        return loss
+
+    def check_overflow(self) -> None:
+        """Raise (a host sync; a collective under torch.distributed) when an f16x3 operand
+        left the fp16 range since the last check: those steps were skipped on the device."""
+        if self.amp:
+            return
+        try:
+            ops.check_f16_overflow(self.dev, all_ranks=True)
+        except FloatingPointError:
+            raise FloatingPointError(
+                "an f16x3 operand exceeded the fp16 range |x| <= 65504 during stage-1 "
+                "training: the affected steps were skipped; train with amp=True") from None
+
+
+class ClassifierTrainer(Stage1Trainer):
+    """Trains every parameter of a ResNet50 ``STDClassifier`` (encoder + WGAP head)."""
+
+    ENCODER = RESNET50
+
+    @staticmethod
+    def param_split(model) -> int:
+        """Elements of the first SGD group (named_parameters order: the encoder, whose layer4
+        is last, then the head — so the reference's second group, layer4 + head, is the
+        tail)."""
+        split = 0
+        for name, p in model.named_parameters():
+            if name.startswith(("encoder.layer4.", "classification_head.")):
+                break
+            split += p.numel()
+        return split
+
+    def _build(self, model: STDClassifier) -> None:
+        enc = model.encoder
+        self.stem = _EConv(enc.conv1, enc.bn1, cin_pad=8)
+        self.layers: List[List[_Block]] = [[_Block(b) for b in layer]
+                                           for layer in (enc.layer1, enc.layer2, enc.layer3,
+                                                         enc.layer4)]
+        self.bns = [m for m in model.modules() if isinstance(m, nn.BatchNorm2d)]
+        self._ws: Dict[str, torch.Tensor] = {}
+        self.wgrad_side = os.environ.get("TCAM_WGRAD_SIDE", "1") != "0"
+        # the fused BN-ReLU backward with a bound-based MFMA scale (TCAM_FUSED_BN_BWD=0: the
+        # three-pass path: backward + channel maxima, scale, re-split)
+        self.fused_bn_bwd = os.environ.get("TCAM_FUSED_BN_BWD", "1") != "0"
+        # the stem's weight gradient as im2col + the 1x1 MFMA GEMM (0: the fp32-MFMA general path)
+        self.stem_im2col = os.environ.get("TCAM_STEM_IM2COL", "1") != "0"
+        # the repack as one batched launch (two on f16x3) once the operand buffers exist
+        self.batched_pack = os.environ.get("TCAM_BATCHED_PACK", "1") != "0"
+        self._pack_items = None
+        self._pack_table = None
+        self._wg_stream = None
+        self._stem_dw = None
+
+    def _workspace(self, key: str, nbytes: int) -> torch.Tensor:
+        cur = self._ws.get(key)
+        if cur is None or cur.numel() < nbytes:
+            if cur is not None and self._wg_stream is not None:
+                cur.record_stream(self._wg_stream)
+            cur = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self.dev)
+            self._ws[key] = cur
+        return cur
+
+    def _convs(self):
+        yield self.stem
+        for layer in self.layers:
+            for b in layer:
+                yield b.c1
+                yield b.c2
+                yield b.c3
+                if b.ds is not None:
+                    yield b.ds
 
     def repack(self):
         """The forward operands of every conv from the flat fp32 weights: once the operand
@@ -387,11 +430,7 @@ class ClassifierTrainer:
               "tcam_bn_relu_bwd_s3s2")
         if not scaled:
             return dy, None, None
-        scale = torch.empty(Cc, device=self.dev, dtype=torch.float32)
-        dy2 = ops.lay_empty("s2", B, H, W, Cc, self.dev)
-        check(lib.tcam_dy_scaled_s2(dy.data_ptr(), P, Cc, amax.data_ptr(), 0, scale.data_ptr(),
-                                    dy2.data_ptr(), _stream()), "tcam_dy_scaled_s2")
-        return dy, dy2, scale
+        return (dy,) + self._dy_scaled(dy, amax)
 
     def _dgrad(self, srcs, w: torch.Tensor, kdiv: Optional[torch.Tensor], sel: int, H: int,
                W: int, k: int, pad: int, c: Optional[_EConv] = None) -> torch.Tensor:
@@ -413,23 +452,6 @@ class ClassifierTrainer:
         check(_lib.load().tcam_zero_up2(t.data_ptr(), out.data_ptr(), gb, B, Cc, H, W, Hi, Wi,
                                         _stream()), "tcam_zero_up2")
         return out
-
-    # -------------------------------------------------------- weight gradients
-    def _side(self, fn, *tensors):
-        """Runs ``fn`` (a weight-gradient launch) on the side stream after everything queued
-        so far on the current stream (TCAM_WGRAD_SIDE=0: inline)."""
-        if not self.wgrad_side:
-            fn()
-            return
-        if self._wg_stream is None:
-            self._wg_stream = torch.cuda.Stream(device=self.dev)
-        side = self._wg_stream
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        for t in tensors:
-            if t is not None:
-                t.record_stream(side)
-        with torch.cuda.stream(side):
-            fn()
 
     def _wgrad11(self, x: torch.Tensor, stride: int, dy: torch.Tensor,
                  dsc: Optional[torch.Tensor], dw: torch.Tensor) -> None:
@@ -492,13 +514,8 @@ class ClassifierTrainer:
     def forward(self, images: torch.Tensor):
         """Train-mode forward: (cl_logits (B, K) fp32, state for :meth:`backward`)."""
         lib = _lib.load()
-        if images.dim() != 4 or images.shape[1] != 3 or not images.is_cuda:
-            raise ValueError("expected a (B, 3, H, W) cuda tensor")
-        if self.param_version() != self._packed_version:
-            self.repack()
-        x = images.contiguous().float()
-        B, _, H, W = x.shape
-        x0 = ops.s3_from_nchw(x, 8, self.fmt)
+        x0 = self._images_s3(images)
+        H, W = images.shape[2:]
         s = self.stem
         H1, W1 = (H + 2 * s.pad - s.k) // s.stride + 1, (W + 2 * s.pad - s.k) // s.stride + 1
         y0 = self._conv([ConvSrc(x0, s.stride)], s, H1, W1)
@@ -533,16 +550,9 @@ class ClassifierTrainer:
                                          i2=i2, y3=y3, m3=m3, i3=i3, yd=yd, md=md, idd=idd,
                                          out=out))
                 f = out
-        Bq, Hf, Wf, Cf = ops.s3_dims(f)
-        K = self.fc.out_features
-        pooled = torch.empty((Bq, Cf), device=self.dev, dtype=torch.float32)
-        logits = torch.empty((Bq, K), device=self.dev, dtype=torch.float32)
-        ws = self._workspace("pool", int(lib.tcam_cls_pool_ws_bytes(Bq, Cf)))
-        check(getattr(lib, f"tcam_cls_fwd_{self.lay}")(
-            f.data_ptr(), Bq, Hf * Wf, Cf, self.fc.weight.data_ptr(), self.fc.bias.data_ptr(), K,
-            pooled.data_ptr(), logits.data_ptr(), ws.data_ptr(), _stream()),
-            f"tcam_cls_fwd_{self.lay}")
-        st["pooled"] = pooled
+        Bq, _, _, Cf = ops.s3_dims(f)
+        logits, st["pooled"] = self._head_fwd(
+            f, self._workspace("pool", int(lib.tcam_cls_pool_ws_bytes(Bq, Cf))))
         st["feat"] = f
         self.model.x_in = images
         return logits, st
@@ -553,23 +563,12 @@ class ClassifierTrainer:
         try:
             self._backward_impl(dlogits.contiguous().float(), st)
         finally:
-            if self._wg_stream is not None:
-                torch.cuda.current_stream(self.dev).wait_stream(self._wg_stream)
+            self._join_side()
 
     def _backward_impl(self, dlogits: torch.Tensor, st) -> None:
         lib = _lib.load()
-        f = st["feat"]
-        B, Hf, Wf, Cf = ops.s3_dims(f)
-        K = self.fc.out_features
-        dpooled = torch.empty((B, Cf), device=self.dev, dtype=torch.float32)
-        check(lib.tcam_cls_bwd(dlogits.data_ptr(), st["pooled"].data_ptr(),
-                               self.fc.weight.data_ptr(), B, K, Cf, 1 if self.amp else 0,
-                               self.g(self.fc.weight).data_ptr(), self.g(self.fc.bias).data_ptr(),
-                               dpooled.data_ptr(), _stream()), "tcam_cls_bwd")
-        dout = ops.lay_empty(self.glay, B, Hf, Wf, Cf, self.dev)
-        check(getattr(lib, f"tcam_pool_bwd_{self.glay}")(dpooled.data_ptr(), B, Hf * Wf, Cf,
-                                                         dout.data_ptr(), _stream()),
-              f"tcam_pool_bwd_{self.glay}")
+        dout = self._head_bwd(dlogits, st["feat"], st["pooled"])
+        B = ops.s3_dims(dout)[0]
         blocks = [b for layer in self.layers for b in layer]
         for bi in range(len(blocks) - 1, -1, -1):
             b, s = blocks[bi], st["blocks"][bi]
@@ -679,104 +678,10 @@ class ClassifierTrainer:
         kdiv = None if self.amp else torch.cat([sc1, scd])
         return self._dgrad([ConvSrc(op1), ConvSrc(srcd)], wcat, kdiv, Cin, Hin, Win, 1, 0)
 
-    # ------------------------------------------------------------- the step
-    def loss_and_grad(self, logits: torch.Tensor, labels: torch.Tensor):
-        """ClLoss on the device: (loss (1,), d loss / d logits (times the AMP scale))."""
-        lab = labels.to(device=self.dev, dtype=torch.int32).contiguous()
-        B, K = logits.shape
-        loss = torch.empty(1, device=self.dev, dtype=torch.float32)
-        dl = torch.empty_like(logits)
-        check(_lib.load().tcam_ce_loss(logits.data_ptr(), lab.data_ptr(), B, K, self.cl_lambda,
-                                       _p(self.scale) if self.amp else None, loss.data_ptr(),
-                                       dl.data_ptr(), _stream()), "tcam_ce_loss")
-        return loss, dl
-
-    def step(self, images: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-        """One optimisation step on a batch; returns the device loss (1,)."""
-        logits, st = self.forward(images)
-        loss, dl = self.loss_and_grad(logits, labels)
-        self.loss_gate.copy_(loss)
-        self.backward(dl, st)
-        if self.amp:   # scaler.unscale_: 1/scale, non-finite check (device)
-            self.found_inf.zero_()
-            check(_lib.load().tcam_amp_unscale(self.grad.data_ptr(), self.grad.numel(),
-                                               self.scale.data_ptr(),
-                                               self.found_inf.data_ptr(), _stream()),
-                  "tcam_amp_unscale")
-        else:
-            # an f16x3 operand beyond the fp16 range made this step invalid: skip it on the
-            # device on every rank (check_overflow() reports it)
-            self.loss_gate.masked_fill_(ops.f16_overflow_flag(self.dev).bool(), float("nan"))
-        self.all_reduce_and_step()
-        self.steps += 1
-        self.last_logits = logits
-        return loss
-
-    def all_reduce_and_step(self) -> None:
-        """DDP average (RCCL all-reduce of the flat gradient + loss slot), rank 0's BN
-        statistics broadcast, the gated SGD step of both parameter groups, repack."""
-        scale = 1.0
-        if dist.is_available() and dist.is_initialized():
-            dist.all_reduce(self._gbuf, op=dist.ReduceOp.SUM)
-            bn = self.bn_flat
-            dist.broadcast(bn, src=0)
-            self.set_bn_flat(bn)
-            scale = 1.0 / dist.get_world_size()
-        lib = _lib.load()
-        n = self.flat.numel()
-        groups = ((0, self.split, self.lrs[0], self._counts_g1),
-                  (self.split, n, self.lrs[1], self.step_counts))
-        for gi, (a, e, lr, cnt) in enumerate(groups):
-            if e <= a:
-                continue
-            p, g, m = self.flat[a:e], self.grad[a:e], self.mom[a:e]
-            if self.amp:
-                gcfg = self.scaler_cfg
-                sc, tr = (self.scale, self.growth_tracker) if gi == 1 else \
-                    (self._scale_shadow, self._tracker_shadow)
-                check(lib.tcam_sgd_step_amp(p.data_ptr(), g.data_ptr(), m.data_ptr(), e - a, lr,
-                                            self.momentum, self.dampening, self.weight_decay,
-                                            1 if self.nesterov else 0, scale,
-                                            self._gbuf[-2:].data_ptr(), cnt.data_ptr(),
-                                            cnt.data_ptr() + 4, sc.data_ptr(), tr.data_ptr(),
-                                            gcfg[0], gcfg[1], gcfg[2], _stream()),
-                      "tcam_sgd_step_amp")
-            else:
-                check(lib.tcam_sgd_step_gated(p.data_ptr(), g.data_ptr(), m.data_ptr(), e - a, lr,
-                                              self.momentum, self.dampening, self.weight_decay,
-                                              1 if self.nesterov else 0, scale,
-                                              self.loss_gate.data_ptr(), cnt.data_ptr(),
-                                              cnt.data_ptr() + 4, _stream()),
-                      "tcam_sgd_step_gated")
-        # one multi-tensor launch for every BN's counter
-        torch._foreach_add_([bn.num_batches_tracked for bn in self.bns], 1)
-        self.repack()
-        self.model.invalidate_plans(ENCODER_PLANS)
-
-    def check_overflow(self) -> None:
-        """Raise (a host sync; a collective under torch.distributed) when an f16x3 operand
-        left the fp16 range since the last check: those steps were skipped on the device."""
-        if self.amp:
-            return
-        try:
-            ops.check_f16_overflow(self.dev, all_ranks=True)
-        except FloatingPointError:
-            raise FloatingPointError(
-                "an f16x3 operand exceeded the fp16 range |x| <= 65504 during stage-1 "
-                "training: the affected steps were skipped; train with amp=True") from None
-
-    @property
-    def applied_steps(self) -> int:
-        return int(self.step_counts[0].item())
-
-    @property
-    def skipped_steps(self) -> int:
-        return int(self.step_counts[1].item())
-
 
 class _TrainForwardCl(torch.autograd.Function):
-    """STDClassifier.forward in train mode as one autograd node: forward =
-    ClassifierTrainer.forward, backward = ClassifierTrainer.backward from d loss / d logits;
+    """STDClassifier.forward in train mode as one autograd node: forward = the stage-1
+    trainer's forward, backward = its backward from d loss / d logits;
     the gradients reach every Parameter through autograd, so the reference's loop
     (``loss = ClLoss(model(x), y); loss.backward(); optimizer.step()``,
     train_wsol.py:1162-1184) and DDP's hooks work unchanged."""
@@ -799,13 +704,15 @@ class _TrainForwardCl(torch.autograd.Function):
 
 
 def train_forward(model: STDClassifier, images: torch.Tensor) -> torch.Tensor:
-    """cl_logits of a ResNet50 STDClassifier in train mode (batch-statistics BatchNorm,
-    running statistics updated), differentiable w.r.t. every parameter when grad mode is
-    on.  Used by STDClassifier.forward when ``model.training``."""
+    """cl_logits of a ResNet50 / VGG16 STDClassifier in train mode (batch-statistics
+    BatchNorm where there is one, running statistics updated), differentiable w.r.t. every
+    parameter when grad mode is on (one autograd node over the trainer's forward /
+    backward).  Used by STDClassifier.forward when ``model.training``."""
+    cls = classifier_trainer_class(model.encoder_name)
     eng = model.__dict__.get("_train_engine")
     amp = getattr(model, "conv_precision", None) == "amp"
-    if eng is None or not eng.views_intact() or eng.amp != amp:
-        eng = ClassifierTrainer(model, amp=amp)
+    if not isinstance(eng, cls) or not eng.views_intact() or eng.amp != amp:
+        eng = cls(model, amp=amp)
         model.__dict__["_train_engine"] = eng
     elif eng.param_version() != eng._packed_version:
         eng.repack()
@@ -813,9 +720,9 @@ def train_forward(model: STDClassifier, images: torch.Tensor) -> torch.Tensor:
         logits = _TrainForwardCl.apply(eng, images, *eng.params)
     else:
         logits, _ = eng.forward(images)
-    # one multi-tensor launch for every BN's counter
-    torch._foreach_add_([bn.num_batches_tracked for bn in eng.bns], 1)
-    model.invalidate_plans(ENCODER_PLANS)
+    if eng.bns:   # the running statistics moved; one multi-tensor launch for the counters
+        torch._foreach_add_([bn.num_batches_tracked for bn in eng.bns], 1)
+        model.invalidate_plans(ENCODER_PLANS)
     return logits
 
 
@@ -833,7 +740,7 @@ def classifier_trainer_class(encoder_name: str):
 
 def make_classifier_trainer(model: STDClassifier, **kw):
     """The stage-1 trainer of ``model``, chosen by its ``encoder_name``; ``kw`` are
-    :class:`ClassifierTrainer`'s constructor arguments (both classes take the same)."""
+    :class:`Stage1Trainer`'s constructor arguments."""
     return classifier_trainer_class(getattr(model, "encoder_name", None))(model, **kw)
 
 
@@ -843,7 +750,7 @@ class _ClStepLR:
     step_size), min_lr); ``trainer.lrs`` follows every ``step()`` (once per epoch,
     main.py:114).  ``state_dict()`` is what the reference checkpoints as 'lr_scheduler'."""
 
-    def __init__(self, trainer: ClassifierTrainer, step_size: int, gamma: float,
+    def __init__(self, trainer: Stage1Trainer, step_size: int, gamma: float,
                  min_lr: float):
         from .training import MyStepLR
         self._trainer = trainer
@@ -866,7 +773,7 @@ class _ClStepLR:
         self._trainer.lrs = [float(v) for v in self._sched.get_last_lr()]
 
 
-def lr_schedule(trainer: ClassifierTrainer, step_size: int, gamma: float,
+def lr_schedule(trainer: Stage1Trainer, step_size: int, gamma: float,
                 min_lr: float) -> _ClStepLR:
     """The stage-1 trainer's per-epoch schedule (opt__lr_scheduler 'mystep')."""
     return _ClStepLR(trainer, step_size, gamma, min_lr)

@@ -716,15 +716,11 @@ class STDClassifier(nn.Module, _HipModelMixin):
             raise NotImplementedError("scale_in != 1 is not on the TCAM hot path")
         self.x_in = x
         x = x.contiguous().float()
-        if self.training and self.encoder_name == RESNET50:
-            # stage-1 training (train_wsol.py:700-714, --freeze_encoder False): batch-statistics
-            # BatchNorm, logits differentiable w.r.t. every parameter (cl_training)
+        if self.training and self.encoder_name in (RESNET50, "vgg16"):
+            # stage-1 training (train_wsol.py:700-714, --freeze_encoder False): logits
+            # differentiable w.r.t. every parameter, batch-statistics BatchNorm on ResNet50
+            # (VGG16 has none: conv + bias + ReLU, 2x2 pools)
             from .cl_training import train_forward
-            self.features = self.features_exp = None
-            return train_forward(self, x)
-        if self.training and self.encoder_name == "vgg16":
-            # the same for the VGG16 classifier (no BatchNorm: conv + bias + ReLU, 2x2 pools)
-            from .vgg_training import train_forward
             self.features = self.features_exp = None
             return train_forward(self, x)
         head = self.classification_head

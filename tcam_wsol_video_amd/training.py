@@ -29,11 +29,11 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 import torch.nn.functional as F
-import torch.distributed as dist
 import torch.nn as nn
 
 from . import _lib, crf, ops
 from ._lib import check, tcam_conv_src
+from .flat_sgd import FlatSGD, _stream
 from .losses import ELB  # noqa: F401  (re-exported: training.ELB)
 from .models import CenterBlock, UnetTCAM
 from .ops import ConvSrc
@@ -41,10 +41,6 @@ from .seeding import prepare_std_cams
 
 # UnetTCAM's eval plans that fold decoder weights / BN
 DECODER_PLANS = ("dec_x6", "dec_f16x3", "dec_amp", "dec")
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
 
 
 
@@ -243,7 +239,7 @@ class _Conv:
         self.dg_cout = 0                             # channels the dgrad produces
 
 
-class DecoderTrainer:
+class DecoderTrainer(FlatSGD):
     """Trains ``model.decoder`` + ``model.segmentation_head`` of a ResNet50 / VGG16 /
     InceptionV3 ``UnetTCAM`` (x6 path: fp32-accurate; the parity path).
 
@@ -269,8 +265,7 @@ class DecoderTrainer:
         if not model.freeze_cl:
             raise NotImplementedError("TCAM trains with freeze_cl=True (README.md:297)")
         self.model = model
-        self.dev = next(model.parameters()).device
-        if self.dev.type != "cuda":
+        if next(model.parameters()).device.type != "cuda":
             raise RuntimeError("training runs on the MI355X HIP path only")
         self.lr, self.momentum, self.dampening = lr, momentum, dampening
         self.weight_decay, self.nesterov = weight_decay, nesterov
@@ -301,7 +296,6 @@ class DecoderTrainer:
         self._enc_pre = None    # (images, version, plan, feats, event) of prefetch_encoder
         self.elb = elb or ELB()
         self.seeder = seeder
-        self.steps = 0
         self.amp = bool(amp)
         # the fp32-accurate step's decoder: "f16x3" (default; TCAM_TRAIN_PREC=x6 restores x6):
         # activations (conv outputs, BN-ReLU outputs) in S2 on the f16x3 convolutions; the
@@ -327,42 +321,23 @@ class DecoderTrainer:
         self.blocks = [(_Conv(b.conv1), _Conv(b.conv2)) for b in dec.blocks]
         self.seg: nn.Conv2d = model.segmentation_head[0]
         # flat parameter / gradient / momentum buffers (parameter order = named_parameters)
-        self.params: List[nn.Parameter] = [p for n, p in model.named_parameters()
-                                           if n.startswith(("decoder.", "segmentation_head."))]
-        n = sum(p.numel() for p in self.params)
-        self.flat = torch.empty(n, device=self.dev, dtype=torch.float32)
-        # gradient + one slot for the step's total loss: the DDP all-reduce carries the
-        # loss with the gradient, and the SGD kernel skips the step on the device when the
-        # summed loss is not finite (train_wsol.py:1181) — every rank sees the same sum
-        # (AMP: one more slot, the GradScaler found_inf flag, summed over the ranks too)
-        self._gbuf = torch.zeros(n + (2 if self.amp else 1), device=self.dev,
-                                 dtype=torch.float32)
-        self.grad = self._gbuf[:n]
-        self.loss_gate = self._gbuf[n:n + 1]
-        self.found_inf = self._gbuf[n + 1:n + 2] if self.amp else None
-        # GradScaler state on the device (torch.cuda.amp.GradScaler: _scale, _growth_tracker)
-        self.scale = torch.full((1,), float(init_scale), device=self.dev, dtype=torch.float32)
-        self.growth_tracker = torch.zeros(1, device=self.dev, dtype=torch.int32)
-        self.mom = torch.zeros(n, device=self.dev, dtype=torch.float32)
-        # device counters: [applied steps, skipped (non-finite) steps]
-        self.step_counts = torch.zeros(2, device=self.dev, dtype=torch.int32)
+        FlatSGD.__init__(self, [p for n, p in model.named_parameters()
+                                if n.startswith(("decoder.", "segmentation_head."))],
+                         amp=amp, init_scale=init_scale)
         self._finite = torch.zeros(1, device=self.dev, dtype=torch.float32)
-        self.views: Dict[int, torch.Tensor] = {}
-        off = 0
-        for p in self.params:
-            k = p.numel()
-            self.flat[off:off + k].copy_(p.detach().reshape(-1))
-            p.data = self.flat[off:off + k].view(p.shape)
-            self.views[id(p)] = self.grad[off:off + k].view(p.shape)
-            off += k
         # the BN modules' own running-statistics buffers are updated in place (never
         # re-bound: DDP and optimizers hold references to the module's tensors)
         self.bns = [c.bn for c in self._convs()]
-        self.zero_bias: Dict[int, torch.Tensor] = {}
         self._bn_ws = None
         self._wg_ws = None
         self._chansum_ws = None
         self.repack()
+
+    PLANS = DECODER_PLANS
+
+    @property
+    def lrs(self) -> List[float]:
+        return [self.lr]   # one parameter group
 
     # ------------------------------------------------------------ helpers
     def set_epoch(self, epoch: int) -> None:
@@ -382,16 +357,6 @@ class DecoderTrainer:
         for c1, c2 in self.blocks:
             out += [c1, c2]
         return out
-
-    def g(self, p: torch.Tensor) -> torch.Tensor:
-        return self.views[id(p)]
-
-    def _zeros(self, n: int) -> torch.Tensor:
-        z = self.zero_bias.get(n)
-        if z is None:
-            z = torch.zeros(n, device=self.dev, dtype=torch.float32)
-            self.zero_bias[n] = z
-        return z
 
     @staticmethod
     def _ws(cur: Optional[torch.Tensor], nbytes: int, dev) -> torch.Tensor:
@@ -428,34 +393,6 @@ class DecoderTrainer:
         check(fn(w.data_ptr(), out.data_ptr(), mode, cout, ctot, kh, kw, c0, sel, cin_pad,
                  _stream()), name)
         return out
-
-    @property
-    def bn_flat(self) -> torch.Tensor:
-        """A copy of every decoder BN running mean / var, concatenated."""
-        return torch.cat([t.reshape(-1) for bn in self.bns
-                          for t in (bn.running_mean, bn.running_var)])
-
-    def set_bn_flat(self, flat: torch.Tensor) -> None:
-        off = 0
-        for bn in self.bns:
-            for t in (bn.running_mean, bn.running_var):
-                k = t.numel()
-                t.copy_(flat[off:off + k].view_as(t))
-                off += k
-
-    def views_intact(self) -> bool:
-        """True while every trainable Parameter still views this trainer's flat buffer
-        (another trainer or a load that replaced ``.data`` breaks the aliasing)."""
-        off = 0
-        base = self.flat.data_ptr()
-        for p in self.params:
-            if p.data_ptr() != base + 4 * off:
-                return False
-            off += p.numel()
-        return True
-
-    def param_version(self) -> int:
-        return sum(p._version for p in self.params)
 
     def _pack_f16(self, c: _Conv, w: torch.Tensor, mode: int, sel: int = 0,
                   kdiv: Optional[torch.Tensor] = None):
@@ -573,21 +510,6 @@ class DecoderTrainer:
                                  self.g(c.bn.weight).data_ptr(), self.g(c.bn.bias).data_ptr(),
                                  P, Cc, self._bn_ws.data_ptr(), _stream()), name)
         return dy
-
-    def _dy_scaled(self, dy: torch.Tensor, amax: Optional[torch.Tensor] = None):
-        """(dy2, scale): the per-channel power-of-two scaled S2 copy of an S3 gradient (max
-        |dy_c| scale_c in [2^14, 2^15)); amax computed here when not given."""
-        B, H, W, Cc = ops.s3_dims(dy)
-        P = B * H * W
-        compute = amax is None
-        if compute:
-            amax = torch.empty(Cc, device=self.dev, dtype=torch.int32)
-        scale = torch.empty(Cc, device=self.dev, dtype=torch.float32)
-        dy2 = ops.lay_empty("s2", B, H, W, Cc, self.dev)
-        check(_lib.load().tcam_dy_scaled_s2(dy.data_ptr(), P, Cc, amax.data_ptr(),
-                                            1 if compute else 0, scale.data_ptr(),
-                                            dy2.data_ptr(), _stream()), "tcam_dy_scaled_s2")
-        return dy2, scale
 
     def _wgrad_s2(self, srcs, dy2: torch.Tensor, dsc: torch.Tensor, dw: torch.Tensor,
                   cout_store: Optional[int] = None):
@@ -889,40 +811,14 @@ class DecoderTrainer:
                 "x6 (TCAM_WGRAD=x6) and run the frozen encoder on x6 "
                 "(model.conv_precision = 'x6')") from None
 
-    @property
-    def applied_steps(self) -> int:
-        """SGD steps applied (steps whose all-reduced loss was finite); a host sync."""
-        return int(self.step_counts[0].item())
-
-    @property
-    def skipped_steps(self) -> int:
-        return int(self.step_counts[1].item())
-
     def backward(self, dF: torch.Tensor, st):
         """Decoder + seg-head backward.  The weight gradients only feed the optimizer, so
-        they run on a side stream (``_wgrad_side``) beside the data-gradient chain, joined
+        they run on a side stream (``_side``) beside the data-gradient chain, joined
         here before returning; TCAM_WGRAD_SIDE=0 keeps them inline."""
         try:
             self._backward_impl(dF, st)
         finally:
-            if self._wg_stream is not None:
-                torch.cuda.current_stream(self.dev).wait_stream(self._wg_stream)
-
-    def _wgrad_side(self, fn, *tensors):
-        """Runs ``fn`` (a weight-gradient launch) on the side stream after everything queued
-        so far on the current stream; the tensors it reads are marked in use by that stream
-        so the allocator does not hand their memory out before it is done."""
-        if not self.wgrad_side:
-            fn()
-            return
-        if self._wg_stream is None:
-            self._wg_stream = torch.cuda.Stream(device=self.dev)
-        side = self._wg_stream
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        for t in tensors:
-            t.record_stream(side)
-        with torch.cuda.stream(side):
-            fn()
+            self._join_side()
 
     def _backward_impl(self, dF: torch.Tensor, st):
         lib = _lib.load()
@@ -947,22 +843,22 @@ class DecoderTrainer:
         if self.f16:
             return self._backward_f16(dF, st, x16, cin)
         dF8 = ops.s3_from_nchw(dF, 8, self.fmt)
-        self._wgrad_side(lambda: self._wgrad([ConvSrc(x16)], dF8, 8, 3, 1,
-                                             self.g(self.seg.weight), cout_store=2), x16, dF8)
+        self._side(lambda: self._wgrad([ConvSrc(x16)], dF8, 8, 3, 1,
+                                       self.g(self.seg.weight), cout_store=2), x16, dF8)
         dx = ops.conv2d_x6([ConvSrc(dF8)], self.seg_dg, self._zeros(cin), cin, H, W, 3, 1, False)
         for bi in range(len(self.blocks) - 1, -1, -1):
             c1, c2 = self.blocks[bi]
             s = st["blocks"][bi]
             Ho, Wo = s["y1"].shape[1], s["y1"].shape[2]
             dy2 = self._bn_bwd(c2, dx, s["a2"], s["y2"], s["m2"], s["i2"])
-            self._wgrad_side(lambda: self._wgrad([ConvSrc(s["a1"])], dy2, c2.cout, 3, 1,
-                                                 self.g(c2.conv.weight)), s["a1"], dy2)
+            self._side(lambda: self._wgrad([ConvSrc(s["a1"])], dy2, c2.cout, 3, 1,
+                                           self.g(c2.conv.weight)), s["a1"], dy2)
             da1 = ops.conv2d_x6([ConvSrc(dy2)], c2.wdg, self._zeros(c2.ctot), c2.ctot, Ho, Wo,
                                 3, 1, False)
             dy1 = self._bn_bwd(c1, da1, s["a1"], s["y1"], s["m1"], s["i1"])
-            self._wgrad_side(lambda: self._wgrad(s["srcs"], dy1, c1.cout, 3, 1,
-                                                 self.g(c1.conv.weight)),
-                             dy1, *[q.t for q in s["srcs"]])
+            self._side(lambda: self._wgrad(s["srcs"], dy1, c1.cout, 3, 1,
+                                           self.g(c1.conv.weight)),
+                       dy1, *[q.t for q in s["srcs"]])
             if bi == 0 and not self.center:
                 break   # the encoder is frozen: no gradient below the first block
             # gradient w.r.t. the block input x (first source channels only)
@@ -986,8 +882,8 @@ class DecoderTrainer:
             c = self.center[ci]
             xin, y, a, mean, inv = st["center"][ci]
             dyc = self._bn_bwd(c, dx, a, y, mean, inv)
-            self._wgrad_side(lambda: self._wgrad([ConvSrc(xin)], dyc, c.cout, 3, 1,
-                                                 self.g(c.conv.weight)), xin, dyc)
+            self._side(lambda: self._wgrad([ConvSrc(xin)], dyc, c.cout, 3, 1,
+                                           self.g(c.conv.weight)), xin, dyc)
             if ci > 0:
                 if c.wdg is None:
                     c.wdg = self._pack(c.conv.weight.data, 1, 0, c.ctot)
@@ -1002,8 +898,8 @@ class DecoderTrainer:
         B, _, H, W = dF.shape
         dF8 = ops.s3_from_nchw(dF, 8, "x6")
         d2, dsc = self._dy_scaled(dF8)
-        self._wgrad_side(lambda: self._wgrad_s2([ConvSrc(x16)], d2, dsc, self.g(self.seg.weight),
-                                                cout_store=2), x16, d2, dsc)
+        self._side(lambda: self._wgrad_s2([ConvSrc(x16)], d2, dsc, self.g(self.seg.weight),
+                                          cout_store=2), x16, d2, dsc)
         # the seg head's data gradient: x6 on dfcams (S3; 8 -> 16 channels, cheap)
         dx = ops.conv2d_x6([ConvSrc(dF8)], self.seg_dg, self._zeros(cin), cin, H, W, 3, 1, False)
         for bi in range(len(self.blocks) - 1, -1, -1):
@@ -1011,12 +907,12 @@ class DecoderTrainer:
             s = st["blocks"][bi]
             Ho, Wo = s["y1"].shape[1], s["y1"].shape[2]
             dy2, sc2 = self._bn_bwd(c2, dx, s["a2"], s["y2"], s["m2"], s["i2"])
-            self._wgrad_side(lambda: self._wgrad_s2([ConvSrc(s["a1"])], dy2, sc2,
-                                                    self.g(c2.conv.weight)), s["a1"], dy2, sc2)
+            self._side(lambda: self._wgrad_s2([ConvSrc(s["a1"])], dy2, sc2,
+                                              self.g(c2.conv.weight)), s["a1"], dy2, sc2)
             da1 = self._dgrad_f16(c2, dy2, sc2, c2.ctot, Ho, Wo)
             dy1, sc1 = self._bn_bwd(c1, da1, s["a1"], s["y1"], s["m1"], s["i1"])
-            self._wgrad_side(lambda: self._wgrad_s2(s["srcs"], dy1, sc1, self.g(c1.conv.weight)),
-                             dy1, sc1, *[q.t for q in s["srcs"]])
+            self._side(lambda: self._wgrad_s2(s["srcs"], dy1, sc1, self.g(c1.conv.weight)),
+                       dy1, sc1, *[q.t for q in s["srcs"]])
             if bi == 0 and not self.center:
                 break   # the encoder is frozen: no gradient below the first block
             # gradient w.r.t. the block input x (first source channels only)
@@ -1034,48 +930,17 @@ class DecoderTrainer:
             c = self.center[ci]
             xin, y, a, mean, inv = st["center"][ci]
             dyc, scc = self._bn_bwd(c, dx, a, y, mean, inv)
-            self._wgrad_side(lambda: self._wgrad_s2([ConvSrc(xin)], dyc, scc,
-                                                    self.g(c.conv.weight)), xin, dyc, scc)
+            self._side(lambda: self._wgrad_s2([ConvSrc(xin)], dyc, scc,
+                                              self.g(c.conv.weight)), xin, dyc, scc)
             if ci > 0:
                 dx = self._dgrad_f16(c, dyc, scc, c.ctot, y.shape[1], y.shape[2])
 
     def all_reduce_and_step(self, gated: bool = False):
-        """DDP gradient average (RCCL all-reduce of the flat buffer), BN buffer broadcast
-        from rank 0, SGD update of the flat weights, repack of the conv operands.
-        ``gated``: the step is skipped on the device when the all-reduced loss slot
-        (``loss_gate``) is not finite (train_wsol.py:1181)."""
-        scale = 1.0
-        if dist.is_available() and dist.is_initialized():
-            dist.all_reduce(self._gbuf if gated else self.grad, op=dist.ReduceOp.SUM)
-            bn = self.bn_flat
-            dist.broadcast(bn, src=0)       # DDP broadcast_buffers: rank 0's statistics
-            self.set_bn_flat(bn)
-            scale = 1.0 / dist.get_world_size()
-        cnt = self.step_counts
-        if self.amp:   # scaler.step(optimizer) + scaler.update(), on the device
-            g, b, itv = self.scaler_cfg
-            check(_lib.load().tcam_sgd_step_amp(
-                self.flat.data_ptr(), self.grad.data_ptr(), self.mom.data_ptr(),
-                self.flat.numel(), self.lr, self.momentum, self.dampening, self.weight_decay,
-                1 if self.nesterov else 0, scale, self._gbuf[-2:].data_ptr(), cnt.data_ptr(),
-                cnt.data_ptr() + 4, self.scale.data_ptr(), self.growth_tracker.data_ptr(),
-                g, b, itv, _stream()), "tcam_sgd_step_amp")
-            # one multi-tensor launch for every BN's counter
-            torch._foreach_add_([bn.num_batches_tracked for bn in self.bns], 1)
-            self.repack()
-            self.model.invalidate_plans(DECODER_PLANS)
-            return
-        gate = self.loss_gate if gated else self._finite
-        check(_lib.load().tcam_sgd_step_gated(self.flat.data_ptr(), self.grad.data_ptr(),
-                                              self.mom.data_ptr(), self.flat.numel(), self.lr,
-                                              self.momentum, self.dampening, self.weight_decay,
-                                              1 if self.nesterov else 0, scale, gate.data_ptr(),
-                                              cnt.data_ptr(), cnt.data_ptr() + 4, _stream()),
-              "tcam_sgd_step_gated")
-        # one multi-tensor launch for every BN's counter
-        torch._foreach_add_([bn.num_batches_tracked for bn in self.bns], 1)
-        self.repack()
-        self.model.invalidate_plans(DECODER_PLANS)
+        """The shared step; ``gated``: the step is skipped on the device when the
+        all-reduced loss slot (``loss_gate``) is not finite (train_wsol.py:1181).  Ungated,
+        the gradient alone is all-reduced and the update always applies (AMP gates on its
+        own slots either way)."""
+        super().all_reduce_and_step(None if gated else self._finite)
 
 
 class MyStepLR(torch.optim.lr_scheduler.StepLR):

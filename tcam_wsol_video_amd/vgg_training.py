@@ -17,8 +17,9 @@ torch.optim.SGD with the reference's two VGG groups (process/instantiators.py:73
 lr_classifier_ratio``), gated on the device as the ResNet50 step is.
 
 Precision: ``prec="f16x3"`` (activations S2, gradients S3) or ``amp=True`` (S1 tensors, the
-device GradScaler), as :class:`~.cl_training.ClassifierTrainer`, whose public surface this
-class has, so checkpoints, the lr schedule and the runner work on either.
+device GradScaler), as :class:`~.cl_training.ClassifierTrainer`: both are a
+:class:`~.cl_training.Stage1Trainer`, so checkpoints, the lr schedule and the runner work on
+either.
 
 Every launch goes to the current stream (no side stream).  Every scratch buffer belongs to
 one kernel and one geometry, is sized by that kernel's own ``*_ws_bytes`` query and is never
@@ -26,16 +27,14 @@ regrown or shared between differently shaped calls.
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
-import torch.distributed as dist
 import torch.nn as nn
 
 from . import _lib, ops
 from ._lib import check, tcam_conv_src
-from .cl_training import ENCODER_PLANS, ClassifierTrainer, _TrainForwardCl, _p, _stream
+from .cl_training import Stage1Trainer, _p, _stream
 from .models import STDClassifier
 from .ops import ConvSrc
 
@@ -102,100 +101,31 @@ def vgg_stack(model) -> List[_VConv]:
     return out
 
 
-class VGG16ClassifierTrainer:
+class VGG16ClassifierTrainer(Stage1Trainer):
     """Trains every parameter of a VGG16 ``STDClassifier`` (encoder + WGAP head)."""
 
-    def __init__(self, model: STDClassifier, lr: float = 0.001, momentum: float = 0.9,
-                 dampening: float = 0.0, weight_decay: float = 1e-4, nesterov: bool = True,
-                 lr_classifier_ratio: float = 10.0, cl_lambda: float = 1.0, amp: bool = False,
-                 init_scale: float = 2.0 ** 16, growth_factor: float = 2.0,
-                 backoff_factor: float = 0.5, growth_interval: int = 2000,
-                 prec: Optional[str] = None):
-        if getattr(model, "encoder_name", None) != VGG16:
-            raise NotImplementedError("VGG16ClassifierTrainer trains the VGG16 STDClassifier")
-        self.model = model
-        self.dev = next(model.parameters()).device
-        if self.dev.type != "cuda":
-            raise RuntimeError("training runs on the MI355X HIP path only")
-        self.momentum, self.dampening = momentum, dampening
-        self.weight_decay, self.nesterov = weight_decay, nesterov
-        self.lr_ratio = float(lr_classifier_ratio)
-        self.lrs = [float(lr), float(lr) * self.lr_ratio]   # the two parameter groups
-        self.cl_lambda = float(cl_lambda)
-        self.amp = bool(amp)
-        prec = prec or os.environ.get("TCAM_TRAIN_PREC", "f16x3")
-        if not self.amp and prec != "f16x3":
-            raise ValueError(f"stage-1 training precision {prec!r}: 'f16x3' (or amp=True)")
-        self.fmt = "amp" if self.amp else "f16x3"
-        self.lay = ops.FMT_LAYOUT[self.fmt]      # activations: S1 / S2
-        self.glay = "s1" if self.amp else "s3"   # gradients: S1 / S3
-        self.scaler_cfg = (float(growth_factor), float(backoff_factor), int(growth_interval))
-        self.convs = vgg_stack(model)
-        self.fc: nn.Linear = model.classification_head.fc
-        # flat parameter / gradient / momentum buffers (named_parameters order:
-        # encoder.features.*, then encoder.conv6.* and the head — the reference's second
-        # group, at lr * lr_classifier_ratio, is the tail; encoder.full_features.* are the
-        # same Parameters under a second name, which named_parameters lists once)
-        named = list(model.named_parameters())
-        self.params: List[nn.Parameter] = [p for _, p in named]
-        n = sum(p.numel() for p in self.params)
-        self.split, tail = 0, False
-        for name, p in named:
+    ENCODER = VGG16
+
+    @staticmethod
+    def param_split(model) -> int:
+        """Elements of the first SGD group (named_parameters order: encoder.features.*, then
+        encoder.conv6.* and the head — the reference's second group — as the tail;
+        encoder.full_features.* are the same Parameters under a second name, which
+        named_parameters lists once)."""
+        split, tail = 0, False
+        for name, p in model.named_parameters():
             if name.startswith("encoder.features."):
                 if tail:
                     raise NotImplementedError("encoder.features.* must precede conv6 / the head")
-                self.split += p.numel()
+                split += p.numel()
             else:
                 tail = True
-        self.flat = torch.empty(n, device=self.dev, dtype=torch.float32)
-        # gradient + the step's loss (+ AMP's found_inf): all-reduced together
-        self._gbuf = torch.zeros(n + (2 if self.amp else 1), device=self.dev,
-                                 dtype=torch.float32)
-        self.grad = self._gbuf[:n]
-        self.loss_gate = self._gbuf[n:n + 1]
-        self.found_inf = self._gbuf[n + 1:n + 2] if self.amp else None
-        self.scale = torch.full((1,), float(init_scale), device=self.dev, dtype=torch.float32)
-        self.growth_tracker = torch.zeros(1, device=self.dev, dtype=torch.int32)
-        # the first group's scaler.update() writes a shadow (one update per step)
-        self._scale_shadow = self.scale.clone()
-        self._tracker_shadow = self.growth_tracker.clone()
-        self.mom = torch.zeros(n, device=self.dev, dtype=torch.float32)
-        # device counters per group: [applied steps, skipped steps]
-        self.step_counts = torch.zeros(2, device=self.dev, dtype=torch.int32)
-        self._counts_g1 = torch.zeros(2, device=self.dev, dtype=torch.int32)
-        self.views: Dict[int, torch.Tensor] = {}
-        off = 0
-        for p in self.params:
-            k = p.numel()
-            self.flat[off:off + k].copy_(p.detach().reshape(-1))
-            p.data = self.flat[off:off + k].view(p.shape)
-            self.views[id(p)] = self.grad[off:off + k].view(p.shape)
-            off += k
-        # the Parameters now live in the flat buffer: an eval plan folded from the old
-        # storage (keyed on data_ptr / _version only) must not survive
-        model.invalidate_plans(ENCODER_PLANS)
-        self.zero_bias: Dict[int, torch.Tensor] = {}
-        self.steps = 0
+        return split
+
+    def _build(self, model: STDClassifier) -> None:
+        self.convs = vgg_stack(model)
         # scratch: one buffer per (kernel, geometry), sized by the kernel's own query
         self._ws: Dict[Tuple, torch.Tensor] = {}
-        self.repack()
-
-    # ------------------------------------------------------------ helpers
-    # (ClassifierTrainer's, unchanged: they touch only attributes both trainers have)
-    lr = ClassifierTrainer.lr
-    trainable_names = ClassifierTrainer.trainable_names
-    loss_t = ClassifierTrainer.loss_t
-    close = ClassifierTrainer.close
-    g = ClassifierTrainer.g
-    _zeros = ClassifierTrainer._zeros
-    views_intact = ClassifierTrainer.views_intact
-    param_version = ClassifierTrainer.param_version
-    _pack = ClassifierTrainer._pack
-    loss_and_grad = ClassifierTrainer.loss_and_grad
-    step = ClassifierTrainer.step
-    check_overflow = ClassifierTrainer.check_overflow
-    applied_steps = ClassifierTrainer.applied_steps
-    skipped_steps = ClassifierTrainer.skipped_steps
 
     def _scratch(self, kernel: str, geom: Tuple, nbytes: int) -> torch.Tensor:
         """The scratch buffer of ``kernel`` at ``geom``: exactly ``nbytes`` (its own size
@@ -229,12 +159,7 @@ class VGG16ClassifierTrainer:
     def forward(self, images: torch.Tensor):
         """Train-mode forward: (cl_logits (B, K) fp32, state for :meth:`backward`)."""
         lib = _lib.load()
-        if images.dim() != 4 or images.shape[1] != 3 or not images.is_cuda:
-            raise ValueError("expected a (B, 3, H, W) cuda tensor")
-        if self.param_version() != self._packed_version:
-            self.repack()
-        x = images.contiguous().float()
-        f = ops.s3_from_nchw(x, 8, self.fmt)
+        f = self._images_s3(images)
         saved = []
         for c in self.convs:
             _, H, W, _ = ops.s3_dims(f)
@@ -247,15 +172,9 @@ class VGG16ClassifierTrainer:
                 f = ops.pool2d_s3(a, 2, 2, 0, "max")
             else:
                 f = a
-        B, Hf, Wf, Cf = ops.s3_dims(f)
-        K = self.fc.out_features
-        pooled = torch.empty((B, Cf), device=self.dev, dtype=torch.float32)
-        logits = torch.empty((B, K), device=self.dev, dtype=torch.float32)
-        ws = self._scratch("cls_pool", (B, Cf), lib.tcam_cls_pool_ws_bytes(B, Cf))
-        check(getattr(lib, f"tcam_cls_fwd_{self.lay}")(
-            f.data_ptr(), B, Hf * Wf, Cf, self.fc.weight.data_ptr(), self.fc.bias.data_ptr(), K,
-            pooled.data_ptr(), logits.data_ptr(), ws.data_ptr(), _stream()),
-            f"tcam_cls_fwd_{self.lay}")
+        B, _, _, Cf = ops.s3_dims(f)
+        logits, pooled = self._head_fwd(
+            f, self._scratch("cls_pool", (B, Cf), lib.tcam_cls_pool_ws_bytes(B, Cf)))
         self.model.x_in = images
         return logits, {"convs": saved, "pooled": pooled, "feat": f}
 
@@ -274,11 +193,7 @@ class VGG16ClassifierTrainer:
                                  _p(amax), P, Cc, ws.data_ptr(), ws.numel(), _stream()), name)
         if self.amp:
             return dz, None, None
-        scale = torch.empty(Cc, device=self.dev, dtype=torch.float32)
-        dy2 = ops.lay_empty("s2", B, H, W, Cc, self.dev)
-        check(lib.tcam_dy_scaled_s2(dz.data_ptr(), P, Cc, amax.data_ptr(), 0, scale.data_ptr(),
-                                    dy2.data_ptr(), _stream()), "tcam_dy_scaled_s2")
-        return dz, dy2, scale
+        return (dz,) + self._dy_scaled(dz, amax)
 
     def _pool_bwd(self, gout: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
         lib = _lib.load()
@@ -332,20 +247,7 @@ class VGG16ClassifierTrainer:
 
     def backward(self, dlogits: torch.Tensor, st) -> None:
         """Gradients of every parameter into the flat buffer from d loss / d logits."""
-        lib = _lib.load()
-        dlogits = dlogits.contiguous().float()
-        f = st["feat"]
-        B, Hf, Wf, Cf = ops.s3_dims(f)
-        K = self.fc.out_features
-        dpooled = torch.empty((B, Cf), device=self.dev, dtype=torch.float32)
-        check(lib.tcam_cls_bwd(dlogits.data_ptr(), st["pooled"].data_ptr(),
-                               self.fc.weight.data_ptr(), B, K, Cf, 1 if self.amp else 0,
-                               self.g(self.fc.weight).data_ptr(), self.g(self.fc.bias).data_ptr(),
-                               dpooled.data_ptr(), _stream()), "tcam_cls_bwd")
-        dout = ops.lay_empty(self.glay, B, Hf, Wf, Cf, self.dev)
-        check(getattr(lib, f"tcam_pool_bwd_{self.glay}")(dpooled.data_ptr(), B, Hf * Wf, Cf,
-                                                         dout.data_ptr(), _stream()),
-              f"tcam_pool_bwd_{self.glay}")
+        dout = self._head_bwd(dlogits.contiguous().float(), st["feat"], st["pooled"])
         for i in range(len(self.convs) - 1, -1, -1):
             c = self.convs[i]
             x, a = st["convs"][i]
@@ -358,58 +260,3 @@ class VGG16ClassifierTrainer:
                 break   # the image needs no gradient
             _, H, W, _ = ops.s3_dims(x)
             dout = self._dgrad(c, op, scale, H, W)
-
-    # ------------------------------------------------------------- the step
-    def all_reduce_and_step(self) -> None:
-        """DDP average (RCCL all-reduce of the flat gradient + loss slot), the gated SGD step
-        of both parameter groups, repack; the model's eval plans are dropped (the kernels
-        write the weights without a version bump)."""
-        scale = 1.0
-        if dist.is_available() and dist.is_initialized():
-            dist.all_reduce(self._gbuf, op=dist.ReduceOp.SUM)
-            scale = 1.0 / dist.get_world_size()
-        lib = _lib.load()
-        n = self.flat.numel()
-        groups = ((0, self.split, self.lrs[0], self._counts_g1),
-                  (self.split, n, self.lrs[1], self.step_counts))
-        for gi, (a, e, lr, cnt) in enumerate(groups):
-            if e <= a:
-                continue
-            p, g, m = self.flat[a:e], self.grad[a:e], self.mom[a:e]
-            if self.amp:
-                gcfg = self.scaler_cfg
-                sc, tr = (self.scale, self.growth_tracker) if gi == 1 else \
-                    (self._scale_shadow, self._tracker_shadow)
-                check(lib.tcam_sgd_step_amp(p.data_ptr(), g.data_ptr(), m.data_ptr(), e - a, lr,
-                                            self.momentum, self.dampening, self.weight_decay,
-                                            1 if self.nesterov else 0, scale,
-                                            self._gbuf[-2:].data_ptr(), cnt.data_ptr(),
-                                            cnt.data_ptr() + 4, sc.data_ptr(), tr.data_ptr(),
-                                            gcfg[0], gcfg[1], gcfg[2], _stream()),
-                      "tcam_sgd_step_amp")
-            else:
-                check(lib.tcam_sgd_step_gated(p.data_ptr(), g.data_ptr(), m.data_ptr(), e - a, lr,
-                                              self.momentum, self.dampening, self.weight_decay,
-                                              1 if self.nesterov else 0, scale,
-                                              self.loss_gate.data_ptr(), cnt.data_ptr(),
-                                              cnt.data_ptr() + 4, _stream()),
-                      "tcam_sgd_step_gated")
-        self.repack()
-        self.model.invalidate_plans(ENCODER_PLANS)
-
-
-def train_forward(model: STDClassifier, images: torch.Tensor) -> torch.Tensor:
-    """cl_logits of a VGG16 STDClassifier in train mode, differentiable w.r.t. every
-    parameter when grad mode is on (one autograd node over the trainer's forward /
-    backward).  Used by STDClassifier.forward when ``model.training``."""
-    eng = model.__dict__.get("_train_engine")
-    amp = getattr(model, "conv_precision", None) == "amp"
-    if not isinstance(eng, VGG16ClassifierTrainer) or not eng.views_intact() or eng.amp != amp:
-        eng = VGG16ClassifierTrainer(model, amp=amp)
-        model.__dict__["_train_engine"] = eng
-    elif eng.param_version() != eng._packed_version:
-        eng.repack()
-    if torch.is_grad_enabled() and any(p.requires_grad for p in eng.params):
-        return _TrainForwardCl.apply(eng, images, *eng.params)
-    logits, _ = eng.forward(images)
-    return logits

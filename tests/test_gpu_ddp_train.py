@@ -163,7 +163,7 @@ def test_stage1_ddp_two_ranks_equal_single_process(cuda, tmp_path):
     ref._gbuf.copy_(grads[0] + grads[1])
     ref.set_bn_flat(bns[0])
     import torch.distributed as dist
-    import tcam_wsol_video_amd.cl_training as CT
+    import tcam_wsol_video_amd.flat_sgd as CT   # the module whose ``dist`` the step reads
     assert not dist.is_initialized()
     # the DDP step on the summed gradient with a world of 2 (its all-reduce and broadcast
     # already applied above): the SGD kernels read the sum times 1/2
