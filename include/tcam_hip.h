@@ -667,6 +667,9 @@ int tcam_chansum_nchw(const float* x, int B, int C, long HW, float* out, void* w
 int tcam_softmax2(const float* fcams, float* S, int B, long HW, void* stream);
 /* TCAM losses on fcams (B, 2, HW) (losses/tcam.py:48-278):
  *   sl   = lam_sl * CrossEntropy(fcams, seeds, ignore_index=-255)      (seeds NULL: off)
+ *          seeds given, lam_sl != 0 and no seed of the whole batch 0 or 1: sl and the total
+ *          are NaN (torch's mean over no element), so a step gated on the total is skipped;
+ *          dfcams then carries the other terms only
  *   crf  = lam_crf * -sum(S * AS) / B,  AS = bilateral(S)              (AS NULL: off)
  *   size = lam_size * 0.5 * sum_c mean_b ELB_t(-sum_hw S[b, c])        (lam_size 0: off)
  * losses[4] = {total, sl, crf, size}; dfcams = d total / d fcams (through the softmax;

@@ -1638,7 +1638,12 @@ __global__ __launch_bounds__(kFinBlock) void loss_finalize_kernel(
         sas += red[2][i];
         size += red[3][i];
     }
-    const float sl = (cfg.use_sl && nv > 0) ? (float)(cfg.lam_sl * ce / nv) : 0.f;
+    // no valid seed in the whole batch: nn.CrossEntropyLoss(reduction="mean", ignore_index)
+    // is 0 / 0 = NaN, and through the total it makes the gated SGD skip the step, as the
+    // reference's isfinite(loss) check does (the gradient keeps no CE term: coef[0] = 0)
+    float sl = 0.f;
+    if (cfg.use_sl && nv > 0) sl = (float)(cfg.lam_sl * ce / nv);
+    else if (cfg.use_sl && cfg.lam_sl != 0.f) sl = __builtin_nanf("");
     const float crf = cfg.use_crf ? (float)(cfg.lam_crf * -sas / B) : 0.f;
     const float sz = cfg.use_size ? (float)(cfg.lam_size * 0.5 * size / B) : 0.f;
     const float ex = extra ? extra[0] : 0.f;
