@@ -70,7 +70,8 @@ __global__ void seghead_cam_kernel(const float* __restrict__ x, const float* __r
 
 // STD_CL CAM, one workgroup per frame.
 //   low = nansum_c w[cls, c] * A[c]          (cams/core.py:176-182)
-//   low = (low - min) / max(low - min)       (core.py:105-111, in place)
+//   low = (low - min) / max(low - min)       (core.py:105-111, in place; torch's min / max:
+//                                              one NaN pixel makes both NaN, the map 0)
 //   nan_to_num                                (inference_wsol.py:323)
 //   cam = bilinear(low -> Ho x Wo, align_corners=False) (inference_wsol.py:342-346)
 constexpr int STD_MAX_HW = 4096;
@@ -95,13 +96,13 @@ __global__ __launch_bounds__(1024) void std_cam_kernel(
     __syncthreads();
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
     float mn = INFINITY;
-    for (int p = threadIdx.x; p < hw; p += blockDim.x) mn = fminf(mn, low[p]);
-    mn = wave_min(mn);
+    for (int p = threadIdx.x; p < hw; p += blockDim.x) mn = min_nan(mn, low[p]);
+    mn = wave_min_nan(mn);
     if (lane == 0) red[wid] = mn;
     __syncthreads();
     if (threadIdx.x == 0) {
         float m = red[0];
-        for (int i = 1; i < nw; ++i) m = fminf(m, red[i]);
+        for (int i = 1; i < nw; ++i) m = min_nan(m, red[i]);
         red[31] = m;
     }
     __syncthreads();
@@ -111,14 +112,14 @@ __global__ __launch_bounds__(1024) void std_cam_kernel(
     for (int p = threadIdx.x; p < hw; p += blockDim.x) {
         float v = low[p] - mn;
         low[p] = v;
-        mx = fmaxf(mx, v);
+        mx = max_nan(mx, v);
     }
-    mx = wave_max(mx);
+    mx = wave_max_nan(mx);
     if (lane == 0) red[wid] = mx;
     __syncthreads();
     if (threadIdx.x == 0) {
         float m = red[0];
-        for (int i = 1; i < nw; ++i) m = fmaxf(m, red[i]);
+        for (int i = 1; i < nw; ++i) m = max_nan(m, red[i]);
         red[30] = m;
     }
     __syncthreads();
@@ -168,12 +169,13 @@ __global__ __launch_bounds__(256) void temporal_max_kernel(const float* __restri
         float scale = 1.f;
         if (t > 0.f) {
             float mx = -INFINITY;
+            // e.max() of re_normalize_cam: NaN if any pixel is (the frame then gives zeros)
             for (int p = threadIdx.x; p < hw; p += blockDim.x)
-                mx = fmaxf(mx, expf((src[p] + 1e-6f) * t));
-            mx = wave_max(mx);
+                mx = max_nan(mx, expf((src[p] + 1e-6f) * t));
+            mx = wave_max_nan(mx);
             if (lane == 0) red[wid] = mx;
             __syncthreads();
-            mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+            mx = max_nan(max_nan(red[0], red[1]), max_nan(red[2], red[3]));
             __syncthreads();
             scale = mx;
         }
@@ -209,14 +211,16 @@ __global__ __launch_bounds__(1024) void frame_expmax_kernel(const float* __restr
     __shared__ float red[16];
     const float* src = cams + (long)blockIdx.x * hw;
     float mx = -INFINITY;
-    for (int p = threadIdx.x; p < hw; p += blockDim.x) mx = fmaxf(mx, expf((src[p] + 1e-6f) * t));
-    mx = wave_max(mx);
+    // e.max(): NaN if any pixel is, so that the whole frame re-normalises to zeros
+    for (int p = threadIdx.x; p < hw; p += blockDim.x)
+        mx = max_nan(mx, expf((src[p] + 1e-6f) * t));
+    mx = wave_max_nan(mx);
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     if (lane == 0) red[wid] = mx;
     __syncthreads();
     if (threadIdx.x == 0) {
         float m = red[0];
-        for (int i = 1; i < (int)(blockDim.x >> 6); ++i) m = fmaxf(m, red[i]);
+        for (int i = 1; i < (int)(blockDim.x >> 6); ++i) m = max_nan(m, red[i]);
         scale[blockIdx.x] = m;
     }
 }
@@ -290,9 +294,14 @@ __global__ void topk_kernel(const float* __restrict__ logits, const int32_t* __r
     if (b >= B) return;
     int t = target[b];
     const float* l = logits + (long)b * C;
-    float lt = l[t];
+    const float lt = l[t];
+    const bool tn = lt != lt;
     int rank = 0;
-    for (int c = 0; c < C; ++c) rank += (l[c] > lt) || (l[c] == lt && c < t);
+    // the stable descending sort places NaN first, NaNs among themselves in index order
+    for (int c = 0; c < C; ++c) {
+        const float v = l[c];
+        rank += (v != v) ? (!tn || c < t) : (!tn && (v > lt || (v == lt && c < t)));
+    }
     top1[b] = rank == 0;
     top5[b] = rank < 5;
 }

@@ -52,6 +52,19 @@ __device__ __forceinline__ float wave_min(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// torch's max() / min() over a tensor: a NaN anywhere is the result (fmaxf / fminf drop it).
+__device__ __forceinline__ float max_nan(float m, float v) { return (v != v || v > m) ? v : m; }
+__device__ __forceinline__ float min_nan(float m, float v) { return (v != v || v < m) ? v : m; }
+__device__ __forceinline__ float wave_max_nan(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max_nan(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_min_nan(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min_nan(v, __shfl_xor(v, o, 64));
+    return v;
+}
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

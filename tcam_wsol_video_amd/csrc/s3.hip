@@ -406,7 +406,8 @@ __global__ void resize_ac_bwd_kernel(const float* __restrict__ dout, float* __re
 
 // ---------------------------------------------------------- STD_CL CAM
 // One workgroup per frame; a wave per position (lanes over channel groups):
-//   low = nansum_c w[cls, c] * A[c]; min-max normalise; nan_to_num;
+//   low = nansum_c w[cls, c] * A[c]; min-max normalise (a NaN pixel makes min and max
+//   NaN, as low.min() / low.max() do: the whole map becomes 0); nan_to_num;
 //   bilinear(align_corners=False) to (Ho, Wo).
 constexpr int STD_MAX_HW = 4096;
 template <class L>
@@ -437,13 +438,13 @@ __global__ __launch_bounds__(1024) void std_cam_s3_kernel(
     }
     __syncthreads();
     float mn = INFINITY;
-    for (int p = threadIdx.x; p < hw; p += blockDim.x) mn = fminf(mn, low[p]);
-    mn = wave_min(mn);
+    for (int p = threadIdx.x; p < hw; p += blockDim.x) mn = min_nan(mn, low[p]);
+    mn = wave_min_nan(mn);
     if (lane == 0) red[wid] = mn;
     __syncthreads();
     if (threadIdx.x == 0) {
         float m = red[0];
-        for (int i = 1; i < nw; ++i) m = fminf(m, red[i]);
+        for (int i = 1; i < nw; ++i) m = min_nan(m, red[i]);
         red[31] = m;
     }
     __syncthreads();
@@ -453,14 +454,14 @@ __global__ __launch_bounds__(1024) void std_cam_s3_kernel(
     for (int p = threadIdx.x; p < hw; p += blockDim.x) {
         const float v = low[p] - mn;
         low[p] = v;
-        mx = fmaxf(mx, v);
+        mx = max_nan(mx, v);
     }
-    mx = wave_max(mx);
+    mx = wave_max_nan(mx);
     if (lane == 0) red[wid] = mx;
     __syncthreads();
     if (threadIdx.x == 0) {
         float m = red[0];
-        for (int i = 1; i < nw; ++i) m = fmaxf(m, red[i]);
+        for (int i = 1; i < nw; ++i) m = max_nan(m, red[i]);
         red[30] = m;
     }
     __syncthreads();
