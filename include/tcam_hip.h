@@ -687,6 +687,33 @@ int tcam_tcam_losses_ex(const float* fcams, const float* S, const int32_t* seeds
                         const float* AS, const float* gx, const float* extra, int B, long HW,
                         float lam_sl, float lam_crf, float lam_size, float elb_t, float* losses,
                         float* dfcams, void* ws, void* stream);
+/* tcam_tcam_losses_ex plus the three further TCAM terms (losses/tcam.py:281-430); each ELB is
+ * averaged over b and carries its own t:
+ *   bgfg = lam_bgfg * ELB_t_bgfg(-(bg_b - fg_b)),  bg_b / fg_b = sum_hw S[b, 0 / 1]
+ *          (BgSizeGreatSizeFgTcams; lam_bgfg 0: off)
+ *   fgsz = lam_fgsz / 2 * (ELB_t_fgsz(fg_size[b] - eps - fg_b / HW)
+ *                          + ELB_t_fgsz(fg_b / HW - fg_size[b] - eps))
+ *          (FgSizeTcams; fg_size (B,) NULL or lam_fgsz 0: off; a NaN fg_size makes the term
+ *          and the total NaN, dfcams stays finite)
+ *   eob  = lam_eob * ELB_t_eob(sum_hw S[b, 1] * (1 - msk[b]))
+ *          (EmptyOutsideBboxTcams; msk (B, HW) of any real values, NULL or lam_eob 0: off)
+ * losses[8] = {total, sl, crf, size, extra[0] (0 when extra is NULL), bgfg, fgsz, eob}; the
+ * total adds the terms that are on in this order.  dfcams = d total / d fcams.  With the three
+ * terms off, losses[0:5] and dfcams hold the bits tcam_tcam_losses_ex writes.  Deterministic
+ * (fixed summation order).  ws: tcam_tcam_loss_terms_ws_bytes(B, HW). */
+size_t tcam_tcam_loss_terms_ws_bytes(int B, long HW);
+int tcam_tcam_losses_terms(const float* fcams, const float* S, const int32_t* seeds,
+                           const float* AS, const float* gx, const float* extra,
+                           const float* fg_size, const float* msk, int B, long HW,
+                           float lam_sl, float lam_crf, float lam_size, float elb_t,
+                           float lam_bgfg, float lam_fgsz, float lam_eob, float t_bgfg,
+                           float t_fgsz, float t_eob, float eps, float* losses, float* dfcams,
+                           void* ws, void* stream);
+/* The teacher's per-frame statistics (learning/train_wsol.py:792-842) from tcam_get_roi's
+ * outputs: msk (B, 1, H, W) = 1 on rows y0..y1-1, columns x0..x1-1 of bbox[b] = (x0, y0, x1,
+ * y1), else 0; fg_size[b] = sum(cams[b] * roi[b]) / (H W), summed in fp64. */
+int tcam_teacher_stats(const float* cams, const uint8_t* roi, const int32_t* bbox, int B,
+                       int H, int W, float* msk, float* fg_size, void* stream);
 /* RgbJointConRanFieldTcams.pair_samples (losses/tcam.py:207-232) and its adjoint.
  * gather: out (G, C, H, L*W) [g, c, y, p*W + x] = src (B, C, H, W) [idx[g*L + p], c, y, x].
  * scatter: dst[b, c, y, x] = (accumulate ? dst : 0) + coef * sum_k mosaic[g_k, c, y,

@@ -20,7 +20,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 from tcam_wsol_video_amd.models import build_r50_tcam  # noqa: E402
-from tcam_wsol_video_amd.training import DecoderTrainer  # noqa: E402
+from tcam_wsol_video_amd.seeding import ROI_LARGEST, GetRoiSingleCam  # noqa: E402
+from tcam_wsol_video_amd.training import DecoderTrainer, teacher_stats  # noqa: E402
 
 PREFETCH = os.environ.get("TCAM_ENC_PREFETCH", "1") != "0"
 GFLOP_TRAIN = 89.57   # 2 MAC_total + 4 MAC_dec+seg per frame
@@ -38,6 +39,10 @@ def main():
     ap.add_argument("--no-crf", action="store_true",
                     help="diagnostic only: CRF term off (lambda 0), to size its share of the "
                          "step; not a TCAM step")
+    ap.add_argument("--terms", action="store_true",
+                    help="the fg-size, bg > fg and empty-outside-box terms on (lambda 1, the "
+                         "reference's defaults), with the teacher's forward, ROI and statistics "
+                         "in every step, as main.py runs them")
     args = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -56,12 +61,26 @@ def main():
     seeds = torch.randint(-1, 2, (n, 224, 224), generator=g, dtype=torch.int32)
     seeds[seeds < 0] = -255
     xd, rd, sd = x.to(dev), raw.to(dev), seeds.to(dev)
-    tr = DecoderTrainer(model, amp=args.amp)
+    tr = DecoderTrainer(model, amp=args.amp, use_bgfg=args.terms, use_fgsz=args.terms,
+                        use_eob=args.terms, fgsz_eps=0.001)
+    teacher = build_r50_tcam(seed=0).to(dev).eval() if args.terms else None
+    getter = GetRoiSingleCam(ROI_LARGEST, 0.05)
+
+    def step():
+        extra = {}
+        if teacher is not None:      # train_wsol.py:768-842 on the device
+            with torch.no_grad():
+                teacher(xd)
+            roi, bbox, _ = getter.batch(teacher.cam)
+            msk, fg = teacher_stats(teacher.cam, roi, bbox)
+            extra = dict(fg_size=fg, msk_bbox=msk)
+        return tr.step(xd, rd, sd, next_images=xd if PREFETCH else None,
+                       next_raw=rd if PREFETCH else None, **extra)
+
     if args.no_crf:
         tr.lam = (tr.lam[0], 0.0) + tuple(tr.lam[2:])
     for _ in range(args.warmup):
-        tr.step(xd, rd, sd, next_images=xd if PREFETCH else None,
-                next_raw=rd if PREFETCH else None)
+        step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -72,8 +91,7 @@ def main():
         # batch would be: its frozen-encoder forward overlaps this step's backward (one
         # encoder forward per step either way; the last one, for a step not taken, is
         # inside the timed region)
-        losses = tr.step(xd, rd, sd, next_images=xd if PREFETCH else None,
-                         next_raw=rd if PREFETCH else None)
+        losses = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -96,6 +114,8 @@ def main():
             "train_prec": "amp" if args.amp else ("f16x3" if tr.f16 else "x6"),
             "applied_steps": tr.applied_steps,
             **({"diagnostic": "CRF term off (not a TCAM step)"} if args.no_crf else {}),
+            **({"terms": "fg size, bg > fg, empty outside box on; teacher forward included",
+                "skipped_steps": tr.skipped_steps} if args.terms else {}),
             "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2),
             "frames_per_step_per_gpu": n, "scaling": "weak",

@@ -239,11 +239,17 @@ def momentum_from_state_dict(model: torch.nn.Module, opt: Optional[dict]) -> Dic
     return out
 
 
-def _loss_t(t: float, use=(True, True, True), rgb: bool = False) -> list:
+TERM_NAMES = {"fgsz": "fg_size_tcams", "bgfg": "bg_size_great_size_fg_tcams",
+              "eob": "empty_outside_bbox_tcams"}     # in get_loss_tcam's order
+
+
+def _loss_t(t: float, use=(True, True, True), rgb: bool = False, terms=None) -> list:
     """MasterLoss.get_t() (losses/master.py:37-41): one [name, t] per instantiated loss in
     get_loss_tcam's order (instantiators.py:148-245: CRF, RGB joint CRF, max-size,
     self-learning); only the ELB-carrying MaxSizePositiveTcams has a t.  ``use`` = (sl,
-    crf, size) enabled, ``rgb`` = RgbJointConRanFieldTcams instantiated."""
+    crf, size) enabled, ``rgb`` = RgbJointConRanFieldTcams instantiated, ``terms`` = {key: t}
+    of the configured FgSizeTcams / BgSizeGreatSizeFgTcams / EmptyOutsideBboxTcams (each has
+    its own ELB; instantiated between max-size and self-learning)."""
     sl, crf, size = use
     out = []
     if crf:
@@ -252,6 +258,9 @@ def _loss_t(t: float, use=(True, True, True), rgb: bool = False) -> list:
         out.append(["rgb_joint_con_ran_field_tcams", 0.0])
     if size:
         out.append(["max_size_positive_tcams", float(t)])
+    for k, name in TERM_NAMES.items():
+        if terms and k in terms:
+            out.append([name, float(terms[k])])
     if sl:
         out.append(["self_learning_tcams", 0.0])
     return out
@@ -288,7 +297,8 @@ def save_checkpoint(trainer, save_dir: str, current_step: int, key: str = CHP_CP
     if hasattr(trainer, "loss_t"):     # stage 1: MasterLoss([ClLoss]).get_t()
         t = trainer.loss_t()
     else:
-        t = _loss_t(trainer.elb.t, trainer.use_cfg, getattr(trainer, "rgb_cfg", None) is not None)
+        t = _loss_t(trainer.elb.t, trainer.use_cfg, getattr(trainer, "rgb_cfg", None) is not None,
+                    {k: e.t for k, e in getattr(trainer, "term_elbs", {}).items()})
     path = os.path.join(save_dir, f"{current_step}_{key}.pth")
     torch.save({CHP_M: _cpu_sd(trainer.model),
                 CHP_O: optimizer_state_dict(trainer.model, hp, mom, ratio,
@@ -334,6 +344,11 @@ def load_checkpoint(trainer, save_dir: str, key: str = CHP_CP, lr_scheduler=None
     t = _t_from(cpt[CHP_T])
     if t is not None and hasattr(trainer, "elb"):
         trainer.elb.t = t
+    if isinstance(cpt[CHP_T], (list, tuple)):     # the further terms' own ELBs, by name
+        by_name = {name: float(v) for name, v in cpt[CHP_T]}
+        for k, e in getattr(trainer, "term_elbs", {}).items():
+            if TERM_NAMES[k] in by_name:
+                e.t = by_name[TERM_NAMES[k]]
     if lr_scheduler is not None and cpt[CHP_LR]:
         lr_scheduler.load_state_dict(cpt[CHP_LR])     # main.py:56-57
     trainer.repack()

@@ -1694,6 +1694,245 @@ __global__ __launch_bounds__(kB) void loss_grad_kernel(const float* __restrict__
     gf[o1] = r1;
 }
 
+// ------------------------------------------- the three further TCAM terms
+// tcam_tcam_losses_terms: the kernels above plus BgSizeGreatSizeFgTcams, FgSizeTcams and
+// EmptyOutsideBboxTcams (losses/tcam.py:281-430).  They are separate kernels so that
+// tcam_tcam_losses(_ex) keep their code; with the three terms off every operation below
+// that feeds losses[0:5] and dfcams is the one of the kernels above, in the same order.
+// Partials per (frame, block): the five above + sum S1 (1 - msk).
+__global__ __launch_bounds__(kB) void loss_partial_terms_kernel(
+    const float* __restrict__ f, const float* __restrict__ S, const int32_t* __restrict__ seeds,
+    const float* __restrict__ AS, const float* __restrict__ msk, long HW, int nchunks,
+    double* __restrict__ part) {
+    const int b = blockIdx.y;
+    const long j0 = (long)blockIdx.x * kLossPix, j1 = min(HW, j0 + kLossPix);
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // S0, S1, CE, valid, S.AS, S1 (1 - msk)
+    for (long j = j0 + threadIdx.x; j < j1; j += kB) {
+        const long o0 = (long)(b * 2) * HW + j, o1 = o0 + HW;
+        const float s0 = S[o0], s1 = S[o1];
+        acc[0] += s0;
+        acc[1] += s1;
+        if (seeds) {
+            const int sd = seeds[(long)b * HW + j];
+            if (sd == 0 || sd == 1) {
+                const float f0 = f[o0], f1 = f[o1];
+                const float m = fmaxf(f0, f1);
+                const float lse = m + logf(expf(f0 - m) + expf(f1 - m));
+                acc[2] += (double)(lse - (sd ? f1 : f0));
+                acc[3] += 1.0;
+            }
+        }
+        if (AS) acc[4] += (double)s0 * AS[o0] + (double)s1 * AS[o1];
+        if (msk) acc[5] += (double)s1 * (1.0 - (double)msk[(long)b * HW + j]);
+    }
+    __shared__ double red[kB / 64][6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q)
+        for (int o = 32; o > 0; o >>= 1) acc[q] += __shfl_xor(acc[q], o, 64);
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int q = 0; q < 6; ++q) red[threadIdx.x >> 6][q] = acc[q];
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        double t = 0.0;
+        for (int w = 0; w < kB / 64; ++w) t += red[w][threadIdx.x];
+        part[((long)b * nchunks + blockIdx.x) * 6 + threadIdx.x] = t;
+    }
+}
+
+struct TermsCfg {
+    float lam_bgfg, lam_fgsz, lam_eob;   // 0 / NULL input: the term is off
+    float t_bgfg, t_fgsz, t_eob;         // each term's own ELB t
+    float eps;                           // FgSizeTcams.eps
+    int use_bgfg, use_fgsz, use_eob;
+};
+
+// ELB.forward on one element, the fp32 formula of the size term above.
+__device__ __forceinline__ void elb_f32(float fx, float t, float& l, float& dl) {
+    if (fx <= -1.f / (t * t)) {
+        l = -(1.f / t) * logf(-fx);
+        dl = -(1.f / t) / fx;
+    } else {
+        l = t * fx - (1.f / t) * logf(1.f / (t * t)) + 1.f / t;
+        dl = t;
+    }
+}
+
+// loss_finalize_kernel + the three terms (each ELB averaged over b):
+//   bgfg = lam * ELB(-(bg - fg)),  bg / fg = sum_hw S[b, 0 / 1]
+//   fgsz = lam / 2 * (ELB(fs - eps - fg / HW) + ELB(fg / HW - fs - eps)),  fs = fg_size[b]
+//   eob  = lam * ELB(sum_hw S[b, 1] (1 - msk[b]))
+// Each barrier argument is formed in fp64 from the fp64 plane sums and cast to fp32 once.
+// coef: [0], [1] as above; [2 + 3b + c] = the per-plane constant of d loss / d S[b, c, :]
+// (size + bgfg + fgsz); [2 + 3b + 2] = the factor of (1 - msk) on plane 1 (eob).
+// losses[8] = {total, sl, crf, size, extra (0 without), bgfg, fgsz, eob}.
+__global__ __launch_bounds__(kFinBlock) void loss_finalize_terms_kernel(
+    const double* __restrict__ part, int B, int nchunks, long HW, LossCfg cfg, TermsCfg tc,
+    const float* __restrict__ fg_size, const float* __restrict__ extra,
+    float* __restrict__ losses, float* __restrict__ coef) {
+    __shared__ double red[7][kFinBlock];
+    double ce = 0.0, nv = 0.0, sas = 0.0, size = 0.0, bgfg = 0.0, fgsz = 0.0, eob = 0.0;
+    const double t = cfg.elb_t, ct = -1.0 / (t * t);
+    for (int b = threadIdx.x; b < B; b += kFinBlock) {
+        double bl[2] = {0.0, 0.0};
+        double out = 0.0;
+        for (int k = 0; k < nchunks; ++k) {
+            const double* p = part + ((long)b * nchunks + k) * 6;
+            bl[0] += p[0];
+            bl[1] += p[1];
+            ce += p[2];
+            nv += p[3];
+            sas += p[4];
+            out += p[5];
+        }
+        float cc[2];
+        for (int c = 0; c < 2; ++c) {
+            const float fx = (float)(-bl[c]);
+            float l, dl;
+            if (fx <= (float)ct) {
+                l = -(1.f / (float)t) * logf(-fx);
+                dl = -(1.f / (float)t) / fx;
+            } else {
+                l = (float)t * fx - (1.f / (float)t) * logf(1.f / ((float)t * (float)t)) +
+                    1.f / (float)t;
+                dl = (float)t;
+            }
+            size += (double)l;
+            cc[c] = cfg.use_size ? -cfg.lam_size * 0.5f * dl / (float)B : 0.f;
+        }
+        if (tc.use_bgfg) {
+            // fx = -(bg - fg): d fx / d S0 = -1, d fx / d S1 = +1
+            float l, dl;
+            elb_f32((float)(-(bl[0] - bl[1])), tc.t_bgfg, l, dl);
+            bgfg += (double)l;
+            const float g = tc.lam_bgfg * dl / (float)B;
+            cc[0] -= g;
+            cc[1] += g;
+        }
+        if (tc.use_fgsz) {
+            // fx1 = fs - eps - fg / HW, fx2 = fg / HW - fs - eps: d / d S1 = -+ 1 / HW
+            const double fg = bl[1] / (double)HW, fs = (double)fg_size[b];
+            float l1, dl1, l2, dl2;
+            elb_f32((float)(fs - (double)tc.eps - fg), tc.t_fgsz, l1, dl1);
+            elb_f32((float)(fg - fs - (double)tc.eps), tc.t_fgsz, l2, dl2);
+            fgsz += (double)l1 + (double)l2;
+            cc[1] += tc.lam_fgsz * 0.5f * (dl2 - dl1) / ((float)B * (float)HW);
+        }
+        float cm = 0.f;
+        if (tc.use_eob) {
+            float l, dl;
+            elb_f32((float)out, tc.t_eob, l, dl);
+            eob += (double)l;
+            cm = tc.lam_eob * dl / (float)B;
+        }
+        coef[2 + 3 * b] = cc[0];
+        coef[2 + 3 * b + 1] = cc[1];
+        coef[2 + 3 * b + 2] = cm;
+    }
+    red[0][threadIdx.x] = ce;
+    red[1][threadIdx.x] = nv;
+    red[2][threadIdx.x] = sas;
+    red[3][threadIdx.x] = size;
+    red[4][threadIdx.x] = bgfg;
+    red[5][threadIdx.x] = fgsz;
+    red[6][threadIdx.x] = eob;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    ce = nv = sas = size = bgfg = fgsz = eob = 0.0;
+    for (int i = 0; i < kFinBlock; ++i) {
+        ce += red[0][i];
+        nv += red[1][i];
+        sas += red[2][i];
+        size += red[3][i];
+        bgfg += red[4][i];
+        fgsz += red[5][i];
+        eob += red[6][i];
+    }
+    float sl = 0.f;
+    if (cfg.use_sl && nv > 0) sl = (float)(cfg.lam_sl * ce / nv);
+    else if (cfg.use_sl && cfg.lam_sl != 0.f) sl = __builtin_nanf("");
+    const float crf = cfg.use_crf ? (float)(cfg.lam_crf * -sas / B) : 0.f;
+    const float sz = cfg.use_size ? (float)(cfg.lam_size * 0.5 * size / B) : 0.f;
+    const float ex = extra ? extra[0] : 0.f;
+    const float v_bgfg = tc.use_bgfg ? (float)((double)tc.lam_bgfg * bgfg / B) : 0.f;
+    const float v_fgsz = tc.use_fgsz ? (float)((double)tc.lam_fgsz * 0.5 * fgsz / B) : 0.f;
+    const float v_eob = tc.use_eob ? (float)((double)tc.lam_eob * eob / B) : 0.f;
+    float total = extra ? ((sl + crf) + sz) + ex : (sl + crf) + sz;
+    if (tc.use_bgfg) total += v_bgfg;
+    if (tc.use_fgsz) total += v_fgsz;
+    if (tc.use_eob) total += v_eob;
+    losses[0] = total;
+    losses[1] = sl;
+    losses[2] = crf;
+    losses[3] = sz;
+    losses[4] = ex;
+    losses[5] = v_bgfg;
+    losses[6] = v_fgsz;
+    losses[7] = v_eob;
+    coef[0] = (cfg.use_sl && nv > 0) ? (float)(cfg.lam_sl / nv) : 0.f;
+    coef[1] = cfg.use_crf ? -2.f * cfg.lam_crf / (float)B : 0.f;
+}
+
+// loss_grad_kernel with the coef layout above and gS_1 += coef[2 + 3b + 2] (1 - msk).
+__global__ __launch_bounds__(kB) void loss_grad_terms_kernel(
+    const float* __restrict__ S, const int32_t* __restrict__ seeds, const float* __restrict__ AS,
+    const float* __restrict__ gx, const float* __restrict__ msk, const float* __restrict__ coef,
+    int B, long HW, float* __restrict__ gf) {
+    const long i = (long)blockIdx.x * kB + threadIdx.x;
+    if (i >= (long)B * HW) return;
+    const long b = i / HW, j = i - b * HW;
+    const long o0 = (b * 2) * HW + j, o1 = o0 + HW;
+    const float s0 = S[o0], s1 = S[o1];
+    float g0 = coef[2 + 3 * b], g1 = coef[2 + 3 * b + 1];
+    if (AS) {
+        g0 += coef[1] * AS[o0];
+        g1 += coef[1] * AS[o1];
+    }
+    if (gx) {
+        g0 += gx[o0];
+        g1 += gx[o1];
+    }
+    if (msk) g1 += coef[2 + 3 * b + 2] * (1.f - msk[b * HW + j]);
+    const float dot = s0 * g0 + s1 * g1;
+    float r0 = s0 * (g0 - dot), r1 = s1 * (g1 - dot);
+    if (seeds) {
+        const int sd = seeds[b * HW + j];
+        if (sd == 0 || sd == 1) {
+            r0 += coef[0] * (s0 - (sd == 0 ? 1.f : 0.f));
+            r1 += coef[0] * (s1 - (sd == 1 ? 1.f : 0.f));
+        }
+    }
+    gf[o0] = r0;
+    gf[o1] = r1;
+}
+
+// The teacher's statistics of a batch of CAMs (train_wsol.py:792-842): the dense box mask
+// msk (B, 1, H, W) = 1 inside bbox[b] = (x0, y0, x1, y1), rows y0..y1-1 and columns x0..x1-1,
+// else 0, and fg_size[b] = sum(cam roi) / (H W) (fp64 sum, one block per frame, fixed order).
+__global__ __launch_bounds__(kB) void teacher_stats_kernel(
+    const float* __restrict__ cams, const uint8_t* __restrict__ roi,
+    const int32_t* __restrict__ bbox, int H, int W, float* __restrict__ msk,
+    float* __restrict__ fg_size) {
+    const int b = blockIdx.x;
+    const long HW = (long)H * W;
+    const int x0 = bbox[4 * b], y0 = bbox[4 * b + 1], x1 = bbox[4 * b + 2], y1 = bbox[4 * b + 3];
+    double s = 0.0;
+    for (long j = threadIdx.x; j < HW; j += kB) {
+        const int y = (int)(j / W), x = (int)(j - (long)y * W);
+        msk[b * HW + j] = (y >= y0 && y < y1 && x >= x0 && x < x1) ? 1.f : 0.f;
+        s += (double)cams[b * HW + j] * (double)roi[b * HW + j];
+    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    __shared__ double red[kB / 64];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int i = 0; i < kB / 64; ++i) t += red[i];
+        fg_size[b] = (float)(t / (double)HW);
+    }
+}
+
 // ------------------------------------------------- RgbJoint frame mosaics
 // RgbJointConRanFieldTcams.pair_samples (losses/tcam.py:207-232): the frames of one group,
 // in frame order, concatenated along the width.  idx (G, L): frame of group g at
@@ -2619,6 +2858,51 @@ extern "C" int tcam_tcam_losses(const float* fcams, const float* S, const int32_
                                 void* ws, void* stream) {
     return tcam_tcam_losses_ex(fcams, S, seeds, AS, nullptr, nullptr, B, HW, lam_sl, lam_crf,
                                lam_size, elb_t, losses, dfcams, ws, stream);
+}
+
+extern "C" size_t tcam_tcam_loss_terms_ws_bytes(int B, long HW) {
+    const long nchunks = (HW + kLossPix - 1) / kLossPix;
+    return (size_t)B * nchunks * 6 * sizeof(double) + (size_t)(2 + 3 * B) * sizeof(float) + 256;
+}
+
+extern "C" int tcam_tcam_losses_terms(const float* fcams, const float* S, const int32_t* seeds,
+                                      const float* AS, const float* gx, const float* extra,
+                                      const float* fg_size, const float* msk, int B, long HW,
+                                      float lam_sl, float lam_crf, float lam_size, float elb_t,
+                                      float lam_bgfg, float lam_fgsz, float lam_eob,
+                                      float t_bgfg, float t_fgsz, float t_eob, float eps,
+                                      float* losses, float* dfcams, void* ws, void* stream) {
+    TCAM_REQUIRE(fcams && S && losses && dfcams && ws && B > 0 && HW > 0 && elb_t > 0.f);
+    TCAM_REQUIRE((gx == nullptr) == (extra == nullptr));
+    TCAM_REQUIRE(t_bgfg > 0.f && t_fgsz > 0.f && t_eob > 0.f && eps >= 0.f);
+    hipStream_t st = as_stream(stream);
+    const int nchunks = (int)((HW + kLossPix - 1) / kLossPix);
+    double* part = (double*)ws;
+    float* coef = (float*)((char*)ws + (size_t)B * nchunks * 6 * sizeof(double));
+    TermsCfg tc{lam_bgfg, lam_fgsz, lam_eob, t_bgfg, t_fgsz, t_eob, eps, lam_bgfg != 0.f,
+                fg_size != nullptr && lam_fgsz != 0.f, msk != nullptr && lam_eob != 0.f};
+    const float* m = tc.use_eob ? msk : nullptr;
+    loss_partial_terms_kernel<<<dim3(nchunks, B), kB, 0, st>>>(fcams, S, seeds, AS, m, HW,
+                                                               nchunks, part);
+    TCAM_CHECK_LAUNCH();
+    LossCfg cfg{lam_sl, lam_crf, lam_size, elb_t, seeds != nullptr, AS != nullptr,
+                lam_size != 0.f};
+    loss_finalize_terms_kernel<<<1, kFinBlock, 0, st>>>(part, B, nchunks, HW, cfg, tc, fg_size,
+                                                        extra, losses, coef);
+    TCAM_CHECK_LAUNCH();
+    loss_grad_terms_kernel<<<cdiv((long)B * HW, kB), kB, 0, st>>>(S, seeds, AS, gx, m, coef, B,
+                                                                   HW, dfcams);
+    TCAM_CHECK_LAUNCH();
+    return TCAM_OK;
+}
+
+extern "C" int tcam_teacher_stats(const float* cams, const uint8_t* roi, const int32_t* bbox,
+                                  int B, int H, int W, float* msk, float* fg_size,
+                                  void* stream) {
+    TCAM_REQUIRE(cams && roi && bbox && msk && fg_size && B > 0 && H > 0 && W > 0);
+    teacher_stats_kernel<<<B, kB, 0, as_stream(stream)>>>(cams, roi, bbox, H, W, msk, fg_size);
+    TCAM_CHECK_LAUNCH();
+    return TCAM_OK;
 }
 
 extern "C" int tcam_mosaic_gather(const float* src, const int32_t* idx, int G, int L, int C,

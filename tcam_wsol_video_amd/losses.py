@@ -10,13 +10,17 @@ builds them unchanged (process/instantiators.py:143-245 for task TCAM):
   MaxSizePositiveTcams  losses/tcam.py:235-278   ELB(-sum S[:, c]) over c in {0, 1}, / 2
   RgbJointConRanFieldTcams losses/tcam.py:158-232 ColorDenseCRFLoss over each knn_tc
                                                  group's width mosaic, mean over groups
-  ELB                   losses/elb.py:15-137     extended log-barrier, t schedule
+  BgSizeGreatSizeFgTcams losses/tcam.py:281-323  ELB(-(bg - fg)), bg / fg = sum_hw S[:, 0 / 1]
+  FgSizeTcams           losses/tcam.py:326-380   (ELB(fs - eps - fg / HW) + ELB(fg / HW - fs -
+                                                 eps)) / 2, fs = ``fg_size`` (B,)
+  EmptyOutsideBboxTcams losses/tcam.py:383-430   ELB(sum_hw S[:, 1] (1 - ``msk_bbox``))
+  ELB                   losses/elb.py:15-137     extended log-barrier, t schedule (one per term)
 
 ``MasterLoss.forward`` evaluates the active TCAM terms in ONE fused pass
 (``training.tcam_losses``: softmax, the bilateral filter, ``tcam_tcam_losses``) and is one
 autograd node whose backward is the fused d loss / d fcams — including
 DenseCRFLossFunction's custom -2 lambda AS / N gradient (crf/dense_crf_loss.py:70-75).
-Terms other than these three are outside the TCAM hot path and raise.
+Terms other than these seven are outside the TCAM hot path and raise.
 """
 from __future__ import annotations
 
@@ -27,7 +31,8 @@ import torch
 import torch.nn as nn
 
 __all__ = ["ELB", "ElementaryLoss", "SelfLearningTcams", "ConRanFieldTcams",
-           "MaxSizePositiveTcams", "RgbJointConRanFieldTcams", "MasterLoss",
+           "MaxSizePositiveTcams", "RgbJointConRanFieldTcams", "FgSizeTcams",
+           "BgSizeGreatSizeFgTcams", "EmptyOutsideBboxTcams", "MasterLoss",
            "group_ordered_frames", "loss_is_on"]
 
 
@@ -184,14 +189,51 @@ class RgbJointConRanFieldTcams(ElementaryLoss):
                           dim=2)[None])
 
 
+class BgSizeGreatSizeFgTcams(ElementaryLoss):
+    """losses/tcam.py:281-323: the background larger than the foreground."""
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        assert isinstance(self.elb, ELB)
+
+
+class FgSizeTcams(ElementaryLoss):
+    """losses/tcam.py:326-380: the foreground size within ``eps`` of the teacher's
+    ``fg_size``; ``set_eps`` comes before the first forward."""
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        assert isinstance(self.elb, ELB)
+        self.eps = 0.0
+        self.eps_already_set = False
+
+    def set_eps(self, eps: float):
+        assert eps >= 0, eps
+        assert isinstance(eps, float), type(eps)
+        self.eps = eps
+        self.eps_already_set = True
+
+
+class EmptyOutsideBboxTcams(ElementaryLoss):
+    """losses/tcam.py:383-430: no foreground outside the teacher's box ``msk_bbox``."""
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        assert isinstance(self.elb, ELB)
+
+
+# training.TERM_KEYS of the three classes above
+_TERM_KEY = {BgSizeGreatSizeFgTcams: "bgfg", FgSizeTcams: "fgsz", EmptyOutsideBboxTcams: "eob"}
+
+
 class _FusedTcamLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, fcams, raw, seeds, lam_sl, lam_crf, lam_size, t, s_rgb, s_xy, rgb,
-                crf_scale):
+                crf_scale, terms=None):
         from .training import tcam_losses
         losses, dF = tcam_losses(fcams.detach().contiguous().float(), raw, seeds,
                                  (lam_sl, lam_crf, lam_size), t, (s_rgb, s_xy), rgb=rgb,
-                                 crf_scale=crf_scale)
+                                 crf_scale=crf_scale, terms=terms)
         ctx.save_for_backward(dF)
         terms = losses[1:]
         ctx.mark_non_differentiable(terms)
@@ -200,7 +242,7 @@ class _FusedTcamLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_total, g_terms):
         (dF,) = ctx.saved_tensors
-        return (dF * g_total.reshape(1, 1, 1, 1),) + (None,) * 10
+        return (dF * g_total.reshape(1, 1, 1, 1),) + (None,) * 11
 
 
 class MasterLoss(nn.Module):
@@ -222,9 +264,9 @@ class MasterLoss(nn.Module):
 
     def add(self, loss_: ElementaryLoss):
         if not isinstance(loss_, (SelfLearningTcams, ConRanFieldTcams, MaxSizePositiveTcams,
-                                  RgbJointConRanFieldTcams)):
-            raise NotImplementedError(f"{type(loss_).__name__}: only the TCAM terms of the "
-                                      f"README run are on the device path")
+                                  RgbJointConRanFieldTcams) + tuple(_TERM_KEY)):
+            raise NotImplementedError(f"{type(loss_).__name__}: only the seven TCAM terms of "
+                                      f"get_loss_tcam are on the device path")
         self.losses.append(loss_)
         self.n_holder.append(loss_.__name__)
 
@@ -243,17 +285,31 @@ class MasterLoss(nn.Module):
 
     def forward(self, epoch: int = 0, fcams: Optional[torch.Tensor] = None,
                 raw_img: Optional[torch.Tensor] = None, seeds: Optional[torch.Tensor] = None,
-                seq_iter=None, frm_iter=None, **unused) -> torch.Tensor:
+                seq_iter=None, frm_iter=None, fg_size: Optional[torch.Tensor] = None,
+                msk_bbox: Optional[torch.Tensor] = None, **unused) -> torch.Tensor:
         assert self.losses != []
         if fcams is None or fcams.dim() != 4 or fcams.shape[1] != 2:
             raise ValueError("TCAM losses take fcams (B, 2, H, W)")
+        terms = {}
         lam = {SelfLearningTcams: 0.0, ConRanFieldTcams: 0.0, MaxSizePositiveTcams: 0.0,
                RgbJointConRanFieldTcams: 0.0}
         t, sig, crf_scale = 1.0, (15.0, 100.0), 1.0
         rgb = None
         for loss in self.losses:
             loss.c_epoch = epoch
+            if isinstance(loss, FgSizeTcams):
+                assert loss.eps_already_set, 'set it first.'
             if not loss.is_on():
+                continue
+            if type(loss) in _TERM_KEY:
+                key = _TERM_KEY[type(loss)]
+                if key in terms:
+                    raise NotImplementedError(f"two {type(loss).__name__} terms")
+                terms[key] = (loss.lambda_, loss.elb.t)
+                if key == "fgsz":
+                    terms[key] += (loss.eps, fg_size)
+                elif key == "eob":
+                    terms[key] += (msk_bbox,)
                 continue
             if isinstance(loss, RgbJointConRanFieldTcams):
                 if rgb is not None:
@@ -279,14 +335,19 @@ class MasterLoss(nn.Module):
             raw = raw_img.to(device=dev, dtype=torch.float32).contiguous()
         if lam[SelfLearningTcams] and seeds is None:
             raise ValueError("SelfLearningTcams needs seeds")
-        total, terms = _FusedTcamLoss.apply(
+        total, vals = _FusedTcamLoss.apply(
             fcams, raw, seeds if lam[SelfLearningTcams] else None, lam[SelfLearningTcams],
             lam[ConRanFieldTcams], lam[MaxSizePositiveTcams], float(t), sig[0], sig[1], rgb,
-            crf_scale)
-        by_type = {SelfLearningTcams: terms[0], ConRanFieldTcams: terms[1],
-                   MaxSizePositiveTcams: terms[2]}
+            crf_scale, terms or None)
+        by_type = {SelfLearningTcams: vals[0], ConRanFieldTcams: vals[1],
+                   MaxSizePositiveTcams: vals[2]}
         if rgb is not None:
-            by_type[RgbJointConRanFieldTcams] = terms[3]
+            by_type[RgbJointConRanFieldTcams] = vals[3]
+        n = 3 + (rgb is not None)
+        for cls, key in _TERM_KEY.items():      # one slot per active term, TERM_KEYS order
+            if key in terms:
+                by_type[cls] = vals[n]
+                n += 1
         zero = torch.zeros((), device=dev)
         self.l_holder = [total] + [by_type[type(l)] if l.is_on() else zero
                                    for l in self.losses]

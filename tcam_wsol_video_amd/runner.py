@@ -135,9 +135,21 @@ def parser(train: bool) -> argparse.ArgumentParser:
         a("--max_sizepos_tc", type=_bool, default=True)
         a("--max_sizepos_tc_lambda", type=float, default=0.01)
         # per-term epoch windows (config.py:400-449; end -1 = never stops, core.py:48-49)
-        for t in ("sl_tc", "crf_tc", "max_sizepos_tc", "rgb_jcrf_tc"):
+        for t in ("sl_tc", "crf_tc", "max_sizepos_tc", "rgb_jcrf_tc", "size_bg_g_fg_tc",
+                  "sizefg_tmp_tc", "empty_out_bb_tc"):
             a(f"--{t}_start_ep", type=int, default=0)
             a(f"--{t}_end_ep", type=int, default=-1)
+        # BgSizeGreatSizeFgTcams / FgSizeTcams / EmptyOutsideBboxTcams (config.py:451-472);
+        # the last two read the teacher's box mask / fg size (train_wsol.py:758-842)
+        for t in ("size_bg_g_fg_tc", "sizefg_tmp_tc", "empty_out_bb_tc"):
+            a(f"--{t}", type=_bool, default=False)
+            a(f"--{t}_lambda", type=float, default=1.0)
+        a("--sizefg_tmp_tc_eps", type=float, default=0.001)
+        a("--sizefg_tmp_tc_knn", type=int, default=0)
+        a("--sizefg_tmp_tc_knn_mode", default="instant")
+        a("--sl_tc_epoch_switch_to_sl", type=int, default=-1,
+          help="epoch from which the best localization model so far (the teacher) is run on "
+               "every batch (config.py:392); -1: never")
         # RgbJointConRanFieldTcams over knn_tc frame groups (config.py:370-375, 436-442)
         a("--knn_tc", type=int, default=0,
           help="frames each side of a sampled frame (batch = batch_size // (2 knn_tc + 1) "
@@ -548,13 +560,55 @@ def train_batches(train: Split, args, rank: int, world: int, epoch: int,
         yield ids, seq, frm
 
 
+def teacher_runs(args, epoch: int) -> bool:
+    """train_wsol.py:758-766: the teacher (the best localization model so far) runs on the
+    batches of ``epoch`` when the self-learning term is on and either the switch epoch is
+    reached or the empty-outside-box term is set and has started."""
+    from .losses import loss_is_on
+    if not (args.sl_tc and loss_is_on(args.sl_tc_start_ep, args.sl_tc_end_ep, epoch)):
+        return False
+    tt = args.sl_tc_epoch_switch_to_sl
+    return bool((tt != -1 and epoch >= tt) or
+                (args.empty_out_bb_tc and epoch >= args.empty_out_bb_tc_start_ep))
+
+
+def check_term_config(args) -> None:
+    """Refuse what the reference refuses (parseit.py:923-928) and what it would crash on: an
+    fg-size / empty-outside-box term active in an epoch in which the teacher does not run
+    hands ``fg_size`` / ``msk_bbox`` = None to the loss (train_wsol.py:758-842, tcam.py:375,
+    418)."""
+    from .losses import loss_is_on
+    if args.sizefg_tmp_tc and args.sizefg_tmp_tc_knn == 0 and \
+            args.sizefg_tmp_tc_knn_mode != "instant":
+        raise SystemExit("--sizefg_tmp_tc_knn 0 needs --sizefg_tmp_tc_knn_mode instant "
+                         "(parseit.py:923-924)")
+    if args.sizefg_tmp_tc and args.sizefg_tmp_tc_knn_mode == "instant" and \
+            args.sizefg_tmp_tc_knn != 0:
+        raise SystemExit("--sizefg_tmp_tc_knn_mode instant needs --sizefg_tmp_tc_knn 0 "
+                         "(parseit.py:926-928)")
+    if args.sizefg_tmp_tc and args.sizefg_tmp_tc_eps < 0:
+        raise SystemExit("--sizefg_tmp_tc_eps must be >= 0 (FgSizeTcams.set_eps, tcam.py:335)")
+    for flag, what in (("sizefg_tmp_tc", "fg_size"), ("empty_out_bb_tc", "msk_bbox")):
+        if not getattr(args, flag):
+            continue
+        win = (getattr(args, flag + "_start_ep"), getattr(args, flag + "_end_ep"))
+        for epoch in range(1, args.max_epochs + 1):
+            if loss_is_on(*win, epoch) and not teacher_runs(args, epoch):
+                raise SystemExit(
+                    f"--{flag} is on in epoch {epoch} but the teacher does not run then, so "
+                    f"{what} would be None (rule: the term's epochs must lie where --sl_tc is "
+                    f"on and epoch >= --sl_tc_epoch_switch_to_sl != -1, or --empty_out_bb_tc "
+                    f"is set and has started; train_wsol.py:758-766)")
+
+
 def train_main(argv=None) -> int:
     """main.py:33-167 + Trainer.train (train_wsol.py:944-1233) for task TCAM."""
     from .camstore import load_roi_thresholds
     from .decay_temp import DecayTemp
     from .losses import ELB
-    from .seeding import GetRoiSingleCam, TCAMSeeder, prepare_std_cams
-    from .training import DecoderTrainer, fill_minibatch, lr_schedule
+    from .seeding import ROI_LARGEST, GetRoiSingleCam, TCAMSeeder, prepare_std_cams
+    from .inference import build_tcam_extractor
+    from .training import DecoderTrainer, fill_minibatch, lr_schedule, teacher_stats
     args = parser(train=True).parse_args(argv)
     if args.freeze_cl is None:
         args.freeze_cl = args.task == TCAM
@@ -564,6 +618,7 @@ def train_main(argv=None) -> int:
         raise SystemExit("main.py trains TCAM with freeze_cl=True (README.md:273-340)")
     if args.rgb_jcrf_tc and args.knn_tc <= 0:
         raise SystemExit("--rgb_jcrf_tc needs --knn_tc > 0 (parseit.py:912-913)")
+    check_term_config(args)
     dev = _init_dist(args)
     rank, world = rank_world()
     model = create_model(**_model_kwargs(args))
@@ -593,7 +648,17 @@ def train_main(argv=None) -> int:
                         rgb_lambda=args.rgb_jcrf_tc_lambda,
                         rgb_sigma_rgb=args.rgb_jcrf_tc_sigma_rgb,
                         rgb_scale=args.rgb_jcrf_tc_scale,
-                        windows={"sl": (args.sl_tc_start_ep, args.sl_tc_end_ep),
+                        use_bgfg=args.size_bg_g_fg_tc, bgfg_lambda=args.size_bg_g_fg_tc_lambda,
+                        use_fgsz=args.sizefg_tmp_tc, fgsz_lambda=args.sizefg_tmp_tc_lambda,
+                        fgsz_eps=float(args.sizefg_tmp_tc_eps),
+                        use_eob=args.empty_out_bb_tc, eob_lambda=args.empty_out_bb_tc_lambda,
+                        windows={"bgfg": (args.size_bg_g_fg_tc_start_ep,
+                                          args.size_bg_g_fg_tc_end_ep),
+                                 "fgsz": (args.sizefg_tmp_tc_start_ep,
+                                          args.sizefg_tmp_tc_end_ep),
+                                 "eob": (args.empty_out_bb_tc_start_ep,
+                                         args.empty_out_bb_tc_end_ep),
+                                 "sl": (args.sl_tc_start_ep, args.sl_tc_end_ep),
                                  "crf": (args.crf_tc_start_ep, args.crf_tc_end_ep),
                                  "size": (args.max_sizepos_tc_start_ep,
                                           args.max_sizepos_tc_end_ep),
@@ -609,6 +674,16 @@ def train_main(argv=None) -> int:
     data = _splits(args, ["train", "val"])
     train, val = data["train"], data["val"]
     roi_fn = GetRoiSingleCam(args.sl_tc_roi_method, args.sl_tc_roi_min_size)
+    # the teacher (train_wsol.py:303, 1735-1756: best_model_loc): a frozen in-memory copy of
+    # the model, the initial one until a validation improves best_loc; built only when some
+    # epoch runs it.  Its ROI is GetRoiSingleCam(ROI_LARGEST) (train_wsol.py:792-795).
+    teacher = None
+    if any(teacher_runs(args, e) for e in range(1, args.max_epochs + 1)):
+        teacher = create_model(**_model_kwargs(args)).to(dev).eval()
+        teacher.load_state_dict(model.state_dict())
+        for p in teacher.parameters():
+            p.requires_grad_(False)
+    teacher_roi = GetRoiSingleCam(ROI_LARGEST, args.sl_tc_roi_min_size)
     roi_th = load_roi_thresholds(args.std_cams_thresh_file) if args.std_cams_thresh_file \
         else None
     tf = FR.get_train_transforms(RESIZE_SIZE, args.crop_size)
@@ -653,6 +728,10 @@ def train_main(argv=None) -> int:
             # model_selection (train_wsol.py:1735-1756): this evaluation is the best one
             if rank == 0 and best_at[key] == len(meters[key]) - 1:
                 CK.save_best_model(model, TCAM, best_dirs[key], at_step)
+            if key == "best_loc" and teacher is not None and \
+                    best_at[key] == len(meters[key]) - 1:
+                teacher.load_state_dict(model.state_dict())     # every rank: the same model
+                teacher.invalidate_plans()
         if rank == 0 and at_step:
             CK.save_tracker(save_dir, at_step, meters)
             CK.keep_last_n_checkpoints(save_dir, args.keep_last_n_checkpoints, key=CK.CHP_TR)
@@ -700,16 +779,30 @@ def train_main(argv=None) -> int:
                 if seq is not None:   # _fill_minibatch on seq_iter / frm_iter (:1132-1133)
                     seq = fill_minibatch(torch.tensor(seq), args.batch_size)
                     frm = fill_minibatch(torch.tensor(frm), args.batch_size)
-                yield x, raw, std, roi, seq, frm
+                fg_size = msk = None
+                if teacher is not None and teacher_runs(args, zepoch):
+                    # train_wsol.py:768-842 on the device: the teacher's CAMs, their largest
+                    # ROI, its box mask and cam-weighted size.  This ROI does not replace the
+                    # seeder's (the reference overwrites it again at :852-859).
+                    with torch.no_grad():
+                        teacher(x)
+                    t_cams = build_tcam_extractor(teacher).compute_cams()
+                    t_roi, t_bbox, _ = teacher_roi.batch(t_cams)
+                    msk, fg_size = teacher_stats(t_cams, t_roi, t_bbox)
+                    teacher.free_mem()
+                    if "fgsz" not in tr.terms_cfg or not tr.terms_lam["fgsz"]:
+                        fg_size = None
+                yield x, raw, std, roi, seq, frm, fg_size, msk
 
         batches = epoch_batches()
         cur = next(batches, None)
         while cur is not None:
             nxt = next(batches, None)
-            x, raw, std, roi, seq, frm = cur
+            x, raw, std, roi, seq, frm, fg_size, msk = cur
+            extra = {} if not tr.terms_cfg else dict(fg_size=fg_size, msk_bbox=msk)
             losses = tr.step(x, raw, std_cams=std, roi=roi, seq_iter=seq, frm_iter=frm,
                              next_images=nxt[0] if nxt is not None else None,
-                             next_raw=nxt[1] if nxt is not None else None)
+                             next_raw=nxt[1] if nxt is not None else None, **extra)
             cur = nxt
             step += 1
             if step % args.checkpoint_save == 0:
@@ -721,7 +814,9 @@ def train_main(argv=None) -> int:
                     CK.keep_last_n_checkpoints(save_dir, args.keep_last_n_checkpoints,
                                                health=health)
         tr.close()             # the unused next-batch lattice / features of the last step
-        tr.elb.update_t()      # on_epoch_end (train_wsol.py:967-976)
+        tr.elb.update_t()      # on_epoch_end (train_wsol.py:967-976): MasterLoss.update_t
+        for e in tr.term_elbs.values():
+            e.update_t()
         tr.check_overflow()
         res = validate(zepoch, step)
         if sched is not None:
@@ -730,6 +825,7 @@ def train_main(argv=None) -> int:
             log.append({"epoch": zepoch, "step": step, "tmp_manager": tmp.get_current_status(),
                         "lr": tr.lr, "skipped_steps": tr.skipped_steps,
                         "losses": [float(v) for v in losses.cpu()] if losses is not None else None,
+                        "loss_names": tr.loss_names(),
                         "val": res, "epoch_s": round(time.perf_counter() - t0, 2)})
             print(json.dumps(log[-1]), flush=True)
     tr.check_overflow()        # all ranks (a collective)

@@ -23,6 +23,7 @@ row).
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 import os
 from typing import Dict, List, Optional, Sequence
@@ -139,10 +140,22 @@ def _scaled_crf(raw_imgs: torch.Tensor, S: torch.Tensor, lam: float, sigma, scal
     return val.detach().reshape(1).float(), gS.float().contiguous()
 
 
+# the three further TCAM terms in their slot order (tcam_tcam_losses_terms, losses[5:8]):
+# BgSizeGreatSizeFgTcams, FgSizeTcams, EmptyOutsideBboxTcams
+TERM_KEYS = ("bgfg", "fgsz", "eob")
+
+
+def _term_input(v, shape, dev, msg: str) -> torch.Tensor:
+    if v is None or tuple(v.shape) != tuple(shape):
+        raise ValueError(f"{msg}, got {None if v is None else tuple(v.shape)}")
+    return v.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+
 def tcam_losses(fcams: torch.Tensor, raw_imgs: Optional[torch.Tensor],
                 seeds: Optional[torch.Tensor], lam=(1.0, 2e-9, 0.01), elb_t: float = 1.0,
                 sigma=(15.0, 100.0), rgb: Optional[tuple] = None, crf_scale: float = 1.0,
-                lattice: Optional["crf.PreparedLattice"] = None):
+                lattice: Optional["crf.PreparedLattice"] = None,
+                terms: Optional[dict] = None):
     """The TCAM MasterLoss of one batch in two kernels + the CRF filter: returns the
     device tensor (total, self-learning, CRF, size) and d total / d fcams.
 
@@ -158,7 +171,12 @@ def tcam_losses(fcams: torch.Tensor, raw_imgs: Optional[torch.Tensor],
     :class:`crf.PreparedLattice` of ``raw_imgs`` built ahead (same sigmas), applied here.
     ``rgb`` = (lam, sigma_rgb, groups): RgbJointConRanFieldTcams (:158-232,
     :func:`rgb_joint_crf`) as a fifth term; the loss tensor then has 5 entries (its value
-    last)."""
+    last).
+    ``terms``: the further terms that are configured, by TERM_KEYS (losses/tcam.py:281-430),
+    each with its own ELB t: ``{"bgfg": (lam, t), "fgsz": (lam, t, eps, fg_size (B,)),
+    "eob": (lam, t, msk_bbox (B, 1, H, W))}``.  The loss tensor grows by one slot per key
+    given, in TERM_KEYS order after the slots above; a zero lambda (a term outside its epoch
+    window) leaves its slot 0 and needs no input.  None / empty: the call above, unchanged."""
     lib = _lib.load()
     dev = fcams.device
     B, _, H, W = fcams.shape
@@ -191,23 +209,69 @@ def tcam_losses(fcams: torch.Tensor, raw_imgs: Optional[torch.Tensor],
     if crf_val is not None:   # the scaled CRF rides the extra-term slot
         extra = crf_val if extra is None else extra + crf_val
         gx = crf_g if gx is None else gx + crf_g
-    losses = torch.empty(4 if extra is None else 5, device=dev, dtype=torch.float32)
+    n_base = 4 if extra is None else 5
     dF = torch.empty_like(fcams)
-    ws = torch.empty(int(lib.tcam_tcam_loss_ws_bytes(B, HW)), dtype=torch.uint8, device=dev)
-    check(lib.tcam_tcam_losses_ex(fcams.data_ptr(), S.data_ptr(),
-                                  seeds.data_ptr() if (seeds is not None and lam_sl) else None,
-                                  AS.data_ptr() if AS is not None else None,
-                                  gx.data_ptr() if gx is not None else None,
-                                  extra.data_ptr() if extra is not None else None, B, HW,
-                                  lam_sl, lam_crf, lam[2], float(elb_t), losses.data_ptr(),
-                                  dF.data_ptr(), ws.data_ptr(), _stream()), "tcam_tcam_losses")
+    ptr = lambda v: v.data_ptr() if v is not None else None
+    if not terms:
+        losses = torch.empty(n_base, device=dev, dtype=torch.float32)
+        ws = torch.empty(int(lib.tcam_tcam_loss_ws_bytes(B, HW)), dtype=torch.uint8, device=dev)
+        check(lib.tcam_tcam_losses_ex(fcams.data_ptr(), S.data_ptr(),
+                                      ptr(seeds) if lam_sl else None, ptr(AS), ptr(gx),
+                                      ptr(extra), B, HW, lam_sl, lam_crf, lam[2], float(elb_t),
+                                      losses.data_ptr(), dF.data_ptr(), ws.data_ptr(),
+                                      _stream()), "tcam_tcam_losses")
+    else:
+        unknown = set(terms) - set(TERM_KEYS)
+        if unknown:
+            raise ValueError(f"tcam_losses: unknown terms {sorted(unknown)}")
+        lam_b, t_b = terms.get("bgfg", (0.0, 1.0))
+        lam_f, t_f, eps, fg_size = terms.get("fgsz", (0.0, 1.0, 0.0, None))
+        lam_e, t_e, msk = terms.get("eob", (0.0, 1.0, None))
+        if lam_f:
+            fg_size = _term_input(fg_size, (B,), dev, "FgSizeTcams needs fg_size (B,)")
+        if lam_e:
+            msk = _term_input(msk, (B, 1, H, W), dev,
+                              "EmptyOutsideBboxTcams needs msk_bbox (B, 1, H, W)")
+        out8 = torch.empty(8, device=dev, dtype=torch.float32)
+        ws = torch.empty(int(lib.tcam_tcam_loss_terms_ws_bytes(B, HW)), dtype=torch.uint8,
+                         device=dev)
+        check(lib.tcam_tcam_losses_terms(
+            fcams.data_ptr(), S.data_ptr(), ptr(seeds) if lam_sl else None, ptr(AS), ptr(gx),
+            ptr(extra), ptr(fg_size) if lam_f else None, ptr(msk) if lam_e else None, B, HW,
+            lam_sl, lam_crf, lam[2], float(elb_t), float(lam_b), float(lam_f), float(lam_e),
+            float(t_b), float(t_f), float(t_e), float(eps), out8.data_ptr(), dF.data_ptr(),
+            ws.data_ptr(), _stream()), "tcam_tcam_losses_terms")
+        losses = torch.cat([out8[:n_base]] + [out8[5 + i:6 + i]
+                                              for i, k in enumerate(TERM_KEYS) if k in terms])
     if crf_val is not None:   # report the two extra terms in their own slots
         losses[2:3].copy_(crf_val)
         if rgb_val is not None:
             losses[4:5].copy_(rgb_val)
         else:
-            losses = losses[:4]
+            losses = losses[:4] if not terms else torch.cat([losses[:4], losses[5:]])
     return losses, dF
+
+
+def teacher_stats(cams: torch.Tensor, roi: torch.Tensor, bbox: torch.Tensor):
+    """The teacher's per-frame statistics (learning/train_wsol.py:792-842) on the device, from
+    the built CAMs (B, H, W) and the ``roi`` (B, H, W) uint8 / ``bbox`` (B, 4) int32 of
+    GetRoiSingleCam.batch: the dense box mask ``msk_bbox`` (B, 1, H, W) and ``fg_size`` (B,) =
+    sum(cam * roi) / (H W).  No host round trip (the reference loops over the frames on the
+    CPU)."""
+    B, H, W = cams.shape
+    dev = cams.device
+    cams = cams.detach().float().contiguous()
+    roi = roi.to(device=dev, dtype=torch.uint8).contiguous()
+    bbox = bbox.to(device=dev, dtype=torch.int32).contiguous()
+    if tuple(roi.shape) != (B, H, W) or tuple(bbox.shape) != (B, 4):
+        raise ValueError(f"teacher_stats: roi {tuple(roi.shape)} / bbox {tuple(bbox.shape)} "
+                         f"vs cams {tuple(cams.shape)}")
+    msk = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32)
+    fg = torch.empty(B, device=dev, dtype=torch.float32)
+    check(_lib.load().tcam_teacher_stats(cams.data_ptr(), roi.data_ptr(), bbox.data_ptr(), B, H,
+                                         W, msk.data_ptr(), fg.data_ptr(), _stream()),
+          "tcam_teacher_stats")
+    return msk, fg
 
 
 def fill_minibatch(x: Optional[torch.Tensor], mbatchsz: int) -> Optional[torch.Tensor]:
@@ -261,7 +325,11 @@ class DecoderTrainer(FlatSGD):
                  backoff_factor: float = 0.5, growth_interval: int = 2000,
                  use_rgb: bool = False, rgb_lambda: float = 2e-9, rgb_sigma_rgb: float = 15.0,
                  rgb_scale: float = 1.0,
-                 windows: Optional[Dict[str, tuple]] = None, prec: Optional[str] = None):
+                 windows: Optional[Dict[str, tuple]] = None, prec: Optional[str] = None,
+                 use_bgfg: bool = False, bgfg_lambda: float = 1.0,
+                 use_fgsz: bool = False, fgsz_lambda: float = 1.0, fgsz_eps: float = 0.001,
+                 use_eob: bool = False, eob_lambda: float = 1.0,
+                 term_elbs: Optional[Dict[str, ELB]] = None):
         if not model.freeze_cl:
             raise NotImplementedError("TCAM trains with freeze_cl=True (README.md:297)")
         self.model = model
@@ -276,8 +344,20 @@ class DecoderTrainer(FlatSGD):
         # batch's (seq_iter, frm_iter) from the knn_tc loader
         self.rgb_cfg = ((float(rgb_lambda), float(rgb_sigma_rgb), float(rgb_scale)) if use_rgb
                         else None)
+        # BgSizeGreatSizeFgTcams / FgSizeTcams / EmptyOutsideBboxTcams (losses/tcam.py:281-430;
+        # --size_bg_g_fg_tc, --sizefg_tmp_tc, --empty_out_bb_tc): {key: lambda} of the
+        # configured ones, each with its own ELB (get_loss_tcam deep-copies one per term)
+        self.terms_cfg = {k: float(v) for k, u, v in (("bgfg", use_bgfg, bgfg_lambda),
+                                                      ("fgsz", use_fgsz, fgsz_lambda),
+                                                      ("eob", use_eob, eob_lambda)) if u}
+        assert isinstance(fgsz_eps, float) and fgsz_eps >= 0, fgsz_eps
+        self.fgsz_eps = fgsz_eps
+        self.elb = elb or ELB()
+        self.term_elbs = {k: (term_elbs or {}).get(k) or copy.deepcopy(self.elb)
+                          for k in self.terms_cfg}
         # per-term epoch windows (*_tc_start_ep, *_tc_end_ep; ElementaryLoss.is_on,
-        # losses/core.py:64-82): {"sl" | "crf" | "size" | "rgb": (start, end)}
+        # losses/core.py:64-82): {"sl" | "crf" | "size" | "rgb" | "bgfg" | "fgsz" | "eob":
+        # (start, end)}
         self.windows = dict(windows or {})
         self.epoch = 0
         self.set_epoch(0)
@@ -294,7 +374,6 @@ class DecoderTrainer(FlatSGD):
         self._wg_stream = None
         self._enc_stream = None
         self._enc_pre = None    # (images, version, plan, feats, event) of prefetch_encoder
-        self.elb = elb or ELB()
         self.seeder = seeder
         self.amp = bool(amp)
         # the fp32-accurate step's decoder: "f16x3" (default; TCAM_TRAIN_PREC=x6 restores x6):
@@ -351,6 +430,17 @@ class DecoderTrainer(FlatSGD):
         self.lam = tuple(lm if on[k] else 0.0
                          for lm, k in zip(self.lam_cfg, ("sl", "crf", "size")))
         self.rgb = self.rgb_cfg if (self.rgb_cfg is not None and on["rgb"]) else None
+        # the configured further terms: lambda, or 0 outside the term's window
+        self.terms_lam = {k: (v if loss_is_on(*self.windows.get(k, (None, None)), self.epoch)
+                              else 0.0) for k, v in self.terms_cfg.items()}
+
+    def loss_names(self) -> List[str]:
+        """The reference's names of the slots of :meth:`step`'s loss vector."""
+        from .checkpoints import TERM_NAMES
+        names = ["total", "self_learning_tcams", "con_ran_field_tcams", "max_size_positive_tcams"]
+        if self.rgb_cfg is not None:
+            names.append("rgb_joint_con_ran_field_tcams")
+        return names + [TERM_NAMES[k] for k in TERM_KEYS if k in self.terms_cfg]
 
     def _convs(self):
         out = list(self.center)
@@ -659,10 +749,14 @@ class DecoderTrainer(FlatSGD):
              seeds: Optional[torch.Tensor] = None, std_cams: Optional[torch.Tensor] = None,
              roi: Optional[torch.Tensor] = None, seq_iter=None,
              frm_iter=None, next_images: Optional[torch.Tensor] = None,
-             next_raw: Optional[torch.Tensor] = None) -> Dict[str, float]:
+             next_raw: Optional[torch.Tensor] = None, fg_size: Optional[torch.Tensor] = None,
+             msk_bbox: Optional[torch.Tensor] = None) -> Dict[str, float]:
         """One optimisation step on a batch; returns the device loss tensor (4,):
         total, self-learning, CRF, size (5 with RgbJointConRanFieldTcams on: its value
-        last).
+        last), then one slot per configured further term in TERM_KEYS order (bg > fg, fg
+        size, empty outside box), 0 outside the term's epoch window.  ``fg_size`` (B,) and
+        ``msk_bbox`` (B, 1, H, W): the teacher's statistics (:func:`teacher_stats`) the fg-size
+        and empty-outside-box terms need while they are on.
 
         Seeds come from the caller, or — as train_wsol.py:846-859 — from the stage-1
         CAMs ``std_cams`` (b, 1, h', w') through ``prepare_std_cams_disq`` and
@@ -685,6 +779,13 @@ class DecoderTrainer(FlatSGD):
             seeds = self.seeder.seeds_i32(cams_inter, roi)
         if (self.use[1] or self.rgb is not None) and raw_imgs is None:
             raise ValueError("the CRF loss needs the raw images (values in [0, 255])")
+        B = images.shape[0]
+        if self.terms_lam.get("fgsz") and (fg_size is None or tuple(fg_size.shape) != (B,)):
+            raise ValueError(f"FgSizeTcams is on: step needs fg_size ({B},)")
+        if self.terms_lam.get("eob") and (msk_bbox is None or tuple(msk_bbox.shape) !=
+                                          (B, 1) + tuple(images.shape[2:])):
+            raise ValueError(f"EmptyOutsideBboxTcams is on: step needs msk_bbox "
+                             f"{(B, 1) + tuple(images.shape[2:])}")
         rgb = None
         if self.rgb_cfg is not None:
             # the term stays in the loss vector (0 outside its epoch window)
@@ -713,10 +814,15 @@ class DecoderTrainer(FlatSGD):
         try:
             cl_logits, fcams, st = self.forward(images)
             use_raw = self.use[1] or (rgb is not None and rgb[2])
+            terms = None
+            if self.terms_cfg:
+                extra_in = {"bgfg": (), "fgsz": (self.fgsz_eps, fg_size), "eob": (msk_bbox,)}
+                terms = {k: (lm, self.term_elbs[k].t) + extra_in[k]
+                         for k, lm in self.terms_lam.items()}
             losses, dF = tcam_losses(fcams, raw_imgs if use_raw else None,
                                      seeds if self.use[0] else None, self.lam, self.elb.t,
                                      self.sigma, rgb=rgb if (rgb and rgb[2]) else None,
-                                     crf_scale=self.crf_scale, lattice=lattice)
+                                     crf_scale=self.crf_scale, lattice=lattice, terms=terms)
         except BaseException:
             # a lattice prepared for this step that was never applied holds a pooled
             # workspace (and a filled hash table): release it
@@ -724,7 +830,8 @@ class DecoderTrainer(FlatSGD):
                 lattice.discard()
             raise
         if rgb is not None and not rgb[2]:   # term off this epoch: a zero slot
-            losses = torch.cat([losses, torch.zeros(1, device=losses.device)])
+            n = len(losses) - len(self.terms_cfg)
+            losses = torch.cat([losses[:n], torch.zeros(1, device=losses.device), losses[n:]])
         self.loss_gate.copy_(losses[:1])
         if self.amp:   # scaler.scale(loss).backward(): d(S loss)/d fcams, an fp16 tensor
             dF = (dF * self.scale).half().float()
