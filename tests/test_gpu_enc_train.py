@@ -70,7 +70,12 @@ def _wgrad11(x, stride, dy, amp=False):
 @pytest.mark.parametrize("dmag", [1.0, 1e-7])
 def test_wgrad11_f16x3_matches_fp64(cuda, B, cin, cout, H, W, stride, dmag):
     """dW = sum_p dy[p] x[s p]: the f16x3 GEMM on S2 x and the per-channel scaled S2 copy of
-    an S3 dy (gradients ~1e-7 included) within fp32 accuracy of the fp64 sum."""
+    an S3 dy (gradients ~1e-7 included) within fp32 accuracy of the fp64 sum.  (More cases of
+    the same check, chosen for the launch plan: tests/test_x_wgrad_plans_gpu.py.)"""
+    check_wgrad11_f16x3(cuda, B, cin, cout, H, W, stride, dmag)
+
+
+def check_wgrad11_f16x3(cuda, B, cin, cout, H, W, stride, dmag):
     g = torch.Generator().manual_seed(cin + cout + H + stride)
     x = torch.randn(B, cin, H, W, generator=g)
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
@@ -93,6 +98,10 @@ def test_wgrad11_f16x3_matches_fp64(cuda, B, cin, cout, H, W, stride, dmag):
 def test_wgrad11_amp_matches_fp64(cuda, B, cin, cout, H, W, stride):
     """The AMP (S1) 1x1 weight gradient: one fp16 product per MAC, fp32 sums, dW rounded to
     fp16 (autocast's weight gradient)."""
+    check_wgrad11_amp(cuda, B, cin, cout, H, W, stride)
+
+
+def check_wgrad11_amp(cuda, B, cin, cout, H, W, stride):
     g = torch.Generator().manual_seed(cin * 3 + cout)
     x = torch.randn(B, cin, H, W, generator=g)
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
