@@ -508,7 +508,7 @@ int tcam_crf_energy(const float* seg, const float* as, long n, int N, float* los
 int tcam_crf_grad(const float* as, const float* grad_out, long n, int N, float* grad,
                   void* stream);
 
-/* ------------------------------------------- training step (csrc/train.hip) */
+/* ----------------------- training step (csrc/train.hip, csrc/train_loss.hip) */
 /* The TCAM decoder + segmentation head train with freeze_cl=True
  * (learning/train_wsol.py:685-884, base/model.py:141-142): these kernels are its
  * forward-with-batch-statistics, backward, losses and optimizer step.  S3 tensors as
