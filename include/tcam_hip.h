@@ -111,6 +111,20 @@ int tcam_conv2d_x6_multi(const tcam_conv_src* srcs, int nsrc, int B,
                          const tcam_conv_dst* dst, int ndst, void* ws, size_t ws_bytes,
                          void* stream);
 int tcam_conv_x6_force_tile(int id);
+/* Host-only queries of the x6 tile table (csrc/conv_x6.hip, kTiles); neither needs a device.
+ * fmt: 0 = x6 (S3), 1 = f16x3 (S2), 2 = AMP fp16 (S1), 3 = f16x3 with S3 output.
+ * tile_info: the tile that forced id `id` runs in format `fmt`, as 13 ints: kind (0 register-
+ * staged, 1 LDS-DMA), BM, BN, WM, WN, stages, M16, IL, LW, PP, FP, grouped-launch kernel,
+ * exact (1 = the id is built for fmt, 0 = the fields are its fallback's).  TCAM_E_ARG outside
+ * 0 <= id < the count tcam_conv_x6_force_tile returns, and for the thin kernel's id.
+ * plan: the tile id the corresponding launch (one frame chunk) would run right now, forced
+ * tile and stream-K state included, or the thin kernel's id; ndst > 1 = the _multi entry
+ * with Cout split evenly.  srcs[i].ptr is checked for alignment and never read.  The
+ * stream-K grid is not part of the plan.  Without a device the CU count is taken as 256. */
+int tcam_conv_x6_tile_info(int fmt, int id, int* out);
+int tcam_conv_x6_plan(const tcam_conv_src* srcs, int nsrc, int B, int Cout, int Hout, int Wout,
+                      int KH, int KW, int pad_h, int pad_w, int fmt, int ndst,
+                      int has_residual, int* tile);
 /* -1 automatic stream-K choice, 0 never (and a tile choice that ignores how full the
  * launch is: each frame's output is then independent of how the frames are batched, e.g.
  * a clip sharded over ranks vs one process), > 0 always, over `grid` blocks (tests). */

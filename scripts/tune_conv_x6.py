@@ -84,6 +84,13 @@ def reference(xs32, specs, ws, bias, k, pad, ho, wo, res=None):
 def main():
     lib = _lib.load()
     ntile = lib.tcam_conv_x6_force_tile(-1)
+    info = (C.c_int * 13)()
+    for t in range(ntile):   # legend: the tile each id runs in this precision
+        if lib.tcam_conv_x6_tile_info(1 if PREC == "f16x3" else 0, t, info) == 0:
+            kind, bm, bn, wm, wn, st, *flags, grp, exact = info
+            names = [n for n, f in zip(("M16", "IL", "LW", "PP", "FP"), flags) if f]
+            print(f"t{t}: {'DMA' if kind else 'REG'} {bm}x{bn} {wm}x{wn} waves S{st} "
+                  f"{' '.join(names)}{'' if exact else ' (fallback)'}")
     lib.tcam_conv_x6_force_streamk(int(os.environ.get("SK", "-1")))
     dbg = int(os.environ.get("DBG", "0"))
     dev = torch.device("cuda")

@@ -70,6 +70,9 @@ SIGNATURES = {
     "tcam_conv_x6_ws_bytes": (C.c_size_t, []),
     "tcam_conv_x6_weight_dims": (_I, [_I, _I, C.POINTER(_I), C.POINTER(_I)]),
     "tcam_conv_x6_force_tile": (_I, [_I]),
+    "tcam_conv_x6_tile_info": (_I, [_I, _I, C.POINTER(_I)]),
+    "tcam_conv_x6_plan": (_I, [C.POINTER(tcam_conv_src), _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
+                               _I, _I, C.POINTER(_I)]),
     "tcam_wgrad_force_fp32": (_I, [_I]),
     "tcam_resample_coeffs": (_I, [_I, _I, _P, _P]),
     "tcam_frames_preprocess": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P,

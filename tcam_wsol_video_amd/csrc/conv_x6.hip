@@ -2317,162 +2317,217 @@ int launch_group_t(ConvX* ps, int n, hipStream_t st) {
     return TCAM_OK;
 }
 
-template <class F, int BM, int BN, int WM, int WN, int STAGES = 1>
-int launch(ConvX& p, hipStream_t st) {
-    return launch_t<ConvTile<F, BM, BN, WM, WN, STAGES>>(p, st);
+// ---- the tile table: every (id, format) that is built, one row each ----
+// Operand format of an entry point (the values are the `fmt` of tcam_conv2d_group and of
+// the queries): X6 = FmtX6 (S3 operands), F16 = FmtF16 (S2 operands, wscale + oflow),
+// H1 = FmtH1 (S1, AMP), F16S3 = FmtF16S3 (S2 operands + wscale, S3 output: the f16x3 data
+// gradient)
+enum class Format : int { X6 = 0, F16 = 1, H1 = 2, F16S3 = 3 };
+constexpr unsigned bit(Format f) { return 1u << (int)f; }
+template <class F>
+constexpr Format format_of() {
+    if constexpr (std::is_same<F, FmtX6>::value) return Format::X6;
+    else if constexpr (std::is_same<F, FmtF16>::value) return Format::F16;
+    else if constexpr (std::is_same<F, FmtH1>::value) return Format::H1;
+    else return Format::F16S3;
+}
+// runs fn(F{}) with the Fmt* type of a runtime format
+template <class Fn>
+auto with_format(Format f, Fn&& fn) {
+    switch (f) {
+        case Format::F16: return fn(FmtF16{});
+        case Format::H1: return fn(FmtH1{});
+        case Format::F16S3: return fn(FmtF16S3{});
+        default: return fn(FmtX6{});
+    }
 }
 
-// ids 0 .. 34 (27 = conv3x3_thin_kernel, not in launch_tile; 30 .. 34 exist for FmtF16 only:
-// their stages need the 2-part operands' smaller LDS footprint)
-constexpr int kNumTiles = 42;
-constexpr int kThinTile = 27;  // forced-tile id of conv3x3_thin_kernel
-int g_force_tile = -1;
+// Tile ids (tcam_conv_x6_force_tile, TCAM_CONV_TILE_MAP, the tuner's tables).  REG: the
+// register-staged ConvTile, DMA: the LDS-DMA ConvTileG (aligned convolutions only);
+// BMxBN, then what differs from a sibling of that shape: W = WMxWN waves, S = ring stages,
+// M16 = 16x16x32 MFMA, IL = next step's pieces interleaved with the MFMA terms, LW =
+// pieces issued by half of the waves (loader waves), PP = ping-pong wave groups, FP =
+// fragment prefetch.  The value is the id and never changes; a new tile takes the next one.
+enum TileId : int {
+    T_REG_128x128 = 0, T_REG_64x128 = 1, T_REG_32x256 = 2, T_REG_128x64 = 3, T_REG_64x64 = 4,
+    T_REG_256x128 = 5, T_REG_256x128_S2 = 6, T_REG_128x128_S2 = 7, T_REG_128x64_S2 = 8,
+    T_REG_64x64_S2 = 9,
+    T_DMA_128x128 = 10, T_DMA_256x128 = 11, T_DMA_128x128_W2x2 = 12, T_DMA_64x128 = 13,
+    T_DMA_256x128_M16 = 14, T_DMA_128x128_M16 = 15, T_DMA_128x128_W2x2_M16 = 16,
+    T_REG_64x64_M16 = 17, T_REG_128x64_M16 = 18, T_REG_128x128_M16 = 19, T_REG_64x128_M16 = 20,
+    T_REG_32x256_M16 = 21,
+    T_DMA_256x128_M16_IL = 22, T_DMA_256x128_M16_LW = 23, T_DMA_256x128_M16_IL_LW = 24,
+    T_DMA_128x128_LW = 25, T_DMA_128x128_M16_LW = 26,
+    kThinTile = 27,  // forced-tile id of conv3x3_thin_kernel: no row, not in launch_tile
+    T_DMA_256x128_M16_LW_PP = 28, T_DMA_128x128_S2_M16_LW_PP = 29,
+    T_DMA_256x128_S3_M16_LW = 30, T_DMA_256x256_LW = 31, T_DMA_128x256_LW = 32,
+    T_DMA_256x128_S3_LW = 33, T_DMA_128x128_S2_M16_LW = 34, T_DMA_256x128_S3_M16_LW_FP = 35,
+    T_DMA_128x128_M16_LW_FP = 36, T_DMA_256x192_M16_LW = 37, T_DMA_256x256_S4_LW = 38,
+    T_DMA_256x256_S4_M16_LW = 39, T_DMA_256x256_S4_M16_LW_FP = 40,
+    T_DMA_256x256_S3_M16_LW_FP = 41,
+    kNumTiles = 42
+};
 
-bool is_g_tile(int id);
+enum : unsigned { M16 = 1, IL = 2, LW = 4, PP = 8, FP = 16, GROUP = 32 };
+struct TileDesc {
+    int id;
+    unsigned fmts;   // bit(Format) of every format the row is built for
+    bool dma;        // ConvTileG (LDS-DMA), else ConvTile (register-staged)
+    int bm, bn, wm, wn, stages;
+    unsigned flags;  // M16 .. FP: the tile's template flags; GROUP: also a grouped-launch kernel
+    constexpr bool has(unsigned f) const { return (flags & f) != 0; }
+};
+constexpr unsigned kX = bit(Format::X6), kF = bit(Format::F16), kH = bit(Format::H1),
+                   kS = bit(Format::F16S3), kXF = kX | kF, kAll = kXF | kH | kS;
+// Two rows share an id where the formats build different types under it (2, 31); their
+// masks are disjoint.  Stages beyond what a row lists exceed the LDS for the other formats
+// (the 2-part FmtF16 / 1-part FmtH1 operands leave room for deeper rings).
+constexpr TileDesc kTiles[] = {
+    {T_REG_128x128, kXF, false, 128, 128, 2, 2, 1, 0},
+    {T_REG_64x128, kXF, false, 64, 128, 2, 2, 1, 0},
+    {T_REG_32x256, kXF, false, 32, 256, 1, 4, 1, 0},
+    {T_REG_32x256, kH, false, 32, 256, 1, 4, 1, M16},
+    {T_REG_128x64, kAll, false, 128, 64, 2, 2, 1, 0},
+    {T_REG_64x64, kXF, false, 64, 64, 2, 2, 1, 0},
+    {T_REG_256x128, kXF, false, 256, 128, 4, 2, 1, 0},
+    {T_REG_256x128_S2, kXF | kH, false, 256, 128, 4, 2, 2, 0},
+    {T_REG_128x128_S2, kXF, false, 128, 128, 2, 2, 2, 0},
+    {T_REG_128x64_S2, kXF, false, 128, 64, 2, 2, 2, 0},
+    {T_REG_64x64_S2, kXF, false, 64, 64, 2, 2, 2, 0},
+    {T_DMA_128x128, kXF, true, 128, 128, 4, 2, 3, 0},
+    {T_DMA_256x128, kXF, true, 256, 128, 4, 2, 2, 0},
+    {T_DMA_128x128_W2x2, kXF, true, 128, 128, 2, 2, 3, 0},
+    {T_DMA_64x128, kXF, true, 64, 128, 2, 2, 3, 0},
+    {T_DMA_256x128_M16, kXF, true, 256, 128, 4, 2, 2, M16},
+    {T_DMA_128x128_M16, kAll, true, 128, 128, 4, 2, 3, M16 | GROUP},
+    {T_DMA_128x128_W2x2_M16, kXF, true, 128, 128, 2, 2, 3, M16},
+    {T_REG_64x64_M16, kAll, false, 64, 64, 2, 2, 1, M16 | GROUP},
+    {T_REG_128x64_M16, kAll, false, 128, 64, 2, 2, 1, M16 | GROUP},
+    {T_REG_128x128_M16, kXF, false, 128, 128, 2, 2, 1, M16},
+    {T_REG_64x128_M16, kAll, false, 64, 128, 2, 2, 1, M16 | GROUP},
+    {T_REG_32x256_M16, kXF, false, 32, 256, 1, 4, 1, M16},
+    {T_DMA_256x128_M16_IL, kXF, true, 256, 128, 4, 2, 2, M16 | IL},
+    {T_DMA_256x128_M16_LW, kXF, true, 256, 128, 4, 2, 2, M16 | LW},
+    {T_DMA_256x128_M16_IL_LW, kXF, true, 256, 128, 4, 2, 2, M16 | IL | LW},
+    {T_DMA_128x128_LW, kXF, true, 128, 128, 4, 2, 3, LW},
+    {T_DMA_128x128_M16_LW, kAll, true, 128, 128, 4, 2, 3, M16 | LW | GROUP},
+    // ping-pong wave groups (one phase apart: one wave of each SIMD on the MFMA pipe while
+    // the other reads LDS)
+    {T_DMA_256x128_M16_LW_PP, kXF, true, 256, 128, 4, 2, 2, M16 | LW | PP},
+    {T_DMA_128x128_S2_M16_LW_PP, kXF, true, 128, 128, 4, 2, 2, M16 | LW | PP},
+    // THREE stages of the 256x128 loader-wave tile (147 KB with 2 parts)
+    {T_DMA_256x128_S3_M16_LW, kF | kH | kS, true, 256, 128, 4, 2, 3, M16 | LW},
+    // 256x256 on 32x32x16 (a wave owns 64x128: 1.33x the FLOP per LDS byte of 256x128):
+    // two stages with 2 parts (131 KB), three with one (96 KB; per K-step 2x the FLOPs of
+    // 256x128 for 1.33x the bytes)
+    {T_DMA_256x256_LW, kF, true, 256, 256, 4, 2, 2, LW},
+    {T_DMA_256x256_LW, kH, true, 256, 256, 4, 2, 3, LW},
+    {T_DMA_128x256_LW, kF | kH, true, 128, 256, 2, 4, 3, LW},   // 147 KB with 2 parts
+    {T_DMA_256x128_S3_LW, kF, true, 256, 128, 4, 2, 3, LW},
+    // TWO stages (64 KB with 2 parts): two blocks per CU, so one block's epilogue overlaps
+    // the other's K loop (the residual 1x1 layers, whose epilogue traffic otherwise idles
+    // the MFMAs of every CU at once)
+    {T_DMA_128x128_S2_M16_LW, kF, true, 128, 128, 4, 2, 2, M16 | LW},
+    // tiles 30 / 26 with fragment prefetch: the next step's LDS fragments read under this
+    // step's MFMAs, two steps of LDS-DMA in flight
+    {T_DMA_256x128_S3_M16_LW_FP, kF, true, 256, 128, 4, 2, 3, M16 | LW | FP},
+    {T_DMA_128x128_M16_LW_FP, kF, true, 128, 128, 4, 2, 3, M16 | LW | FP},
+    // two stages (115 KB): a launch whose 192-pixel tiles make exactly one round where 128
+    // makes two and 256 leaves CUs idle (InceptionV3's SPG heads at 8 x 39^2: 256 tiles on
+    // 256 CUs)
+    {T_DMA_256x192_M16_LW, kF, true, 256, 192, 4, 2, 2, M16 | LW},
+    // round 5: deeper rings for the one-part operands (one MFMA product per fragment: the K
+    // loop waits on L2 / HBM latency, so more steps in flight): 256x256 with four stages
+    // (128 KB, three steps in flight) on 32x32x16 / 16x16x32 (five stages exceed the LDS by
+    // the kernel's own 4-byte word), and the 16x16x32 forms with fragment prefetch
+    {T_DMA_256x256_S4_LW, kH, true, 256, 256, 4, 2, 4, LW},
+    {T_DMA_256x256_S4_M16_LW, kH, true, 256, 256, 4, 2, 4, M16 | LW},
+    {T_DMA_256x256_S4_M16_LW_FP, kH, true, 256, 256, 4, 2, 4, M16 | LW | FP},
+    {T_DMA_256x256_S3_M16_LW_FP, kH, true, 256, 256, 4, 2, 3, M16 | LW | FP},
+};
+constexpr int kNumRows = sizeof(kTiles) / sizeof(kTiles[0]);
 
+// row of `id` built for one of the formats in `fmts`, or -1
+constexpr int find_row(unsigned fmts, int id) {
+    for (int i = 0; i < kNumRows; ++i)
+        if (kTiles[i].id == id && (kTiles[i].fmts & fmts)) return i;
+    return -1;
+}
+// LDS-DMA tile in the formats that build it (aligned convolutions only)
+bool is_g_tile(int id) { const int r = find_row(kAll, id); return r >= 0 && kTiles[r].dma; }
+bool is_f16_only_tile(int id) { return find_row(kX, id) < 0; }
+bool is_group_tile(int id) { const int r = find_row(kAll, id); return r >= 0 && kTiles[r].has(GROUP); }
+// tiles on the 16x16x32 MFMA (epilogue16: the per-group destinations of a grouped or
+// multi-destination launch); an id the format does not build answers for the formats that do
+bool is_m16_tile(Format fmt, int id) {
+    int r = find_row(bit(fmt), id);
+    if (r < 0) r = find_row(kAll, id);
+    return r >= 0 && kTiles[r].has(M16);
+}
+
+// The row that runs for (fmt, id).  An id the format does not build runs the nearest tile it
+// does: FmtX6 / FmtF16 the two-stage 256x128 loader-wave tile, FmtH1 / FmtF16S3 its
+// three-stage form for an LDS-DMA id and the register-staged 128x64 tile otherwise.
+constexpr int resolve(Format fmt, int id) {
+    const int r = find_row(bit(fmt), id);
+    if (r >= 0) return r;
+    if (fmt == Format::X6 || fmt == Format::F16) return find_row(bit(fmt), T_DMA_256x128_M16_LW);
+    const int any = find_row(kAll, id);
+    return find_row(bit(fmt), any >= 0 && kTiles[any].dma ? T_DMA_256x128_S3_M16_LW
+                                                          : T_REG_128x64_M16);
+}
+
+template <class F, int I>
+struct TileAtT {
+    static constexpr TileDesc d = kTiles[I];
+    using type = typename std::conditional<
+        d.dma,
+        ConvTileG<F, d.bm, d.bn, d.wm, d.wn, d.stages, d.has(M16), d.has(IL), d.has(LW),
+                  d.has(PP), d.has(FP)>,
+        ConvTile<F, d.bm, d.bn, d.wm, d.wn, d.stages, d.has(M16)>>::type;
+};
+template <class F, int I>
+using TileAt = typename TileAtT<F, I>::type;
+
+template <class F, int I>
+constexpr bool built(unsigned need = 0) {
+    return (kTiles[I].fmts & bit(format_of<F>())) != 0 && (kTiles[I].flags & need) == need;
+}
+// fn(integral_constant<int, row>): the one place a runtime row index becomes a type
+template <class Fn, int... I>
+int with_row(int row, Fn&& fn, std::integer_sequence<int, I...>) {
+    int rc = TCAM_E_ARG;
+    (void)(... || (row == I && ((rc = fn(std::integral_constant<int, I>{})), true)));
+    return rc;
+}
+constexpr std::make_integer_sequence<int, kNumRows> kRows{};
+
+// A row is instantiated only for its formats, its grouped kernel only where it has GROUP.
 template <class F>
 int launch_tile(int id, ConvX& p, hipStream_t st) {
-    if constexpr (!std::is_same<typename F::Out, F>::value) {
-        // FmtF16S3 (the f16x3 data gradients of training): the tiles the chooser picks on
-        // those shapes; any other id maps to the nearest of them
-        switch (id) {
-            case 3: return launch<F, 128, 64, 2, 2>(p, st);
-            case 15: return launch_t<ConvTileG<F, 128, 128, 4, 2, 3, true>>(p, st);
-            case 17: return launch_t<ConvTile<F, 64, 64, 2, 2, 1, true>>(p, st);
-            case 18: return launch_t<ConvTile<F, 128, 64, 2, 2, 1, true>>(p, st);
-            case 20: return launch_t<ConvTile<F, 64, 128, 2, 2, 1, true>>(p, st);
-            case 26: return launch_t<ConvTileG<F, 128, 128, 4, 2, 3, true, false, true>>(p, st);
-            case 30: return launch_t<ConvTileG<F, 256, 128, 4, 2, 3, true, false, true>>(p, st);
-            default: break;
-        }
-        if (!is_g_tile(id)) return launch_t<ConvTile<F, 128, 64, 2, 2, 1, true>>(p, st);
-        return launch_t<ConvTileG<F, 256, 128, 4, 2, 3, true, false, true>>(p, st);
-    } else if constexpr (F::NP == 1) {
-        // FmtH1 (AMP training): the tiles the chooser picks; any other id maps to the nearest
-        // of them (LDS-DMA or register-staged)
-        switch (id) {
-            case 2: return launch_t<ConvTile<F, 32, 256, 1, 4, 1, true>>(p, st);
-            case 3: return launch<F, 128, 64, 2, 2>(p, st);
-            case 6: return launch<F, 256, 128, 4, 2, 2>(p, st);
-            case 15: return launch_t<ConvTileG<F, 128, 128, 4, 2, 3, true>>(p, st);
-            case 17: return launch_t<ConvTile<F, 64, 64, 2, 2, 1, true>>(p, st);
-            case 18: return launch_t<ConvTile<F, 128, 64, 2, 2, 1, true>>(p, st);
-            case 20: return launch_t<ConvTile<F, 64, 128, 2, 2, 1, true>>(p, st);
-            case 26: return launch_t<ConvTileG<F, 128, 128, 4, 2, 3, true, false, true>>(p, st);
-            // one-part operands: 256x256 / 128x256 LDS-DMA on 32x32x16 with loader waves,
-            // three stages in 96 KB (per K-step 2x the FLOPs of 256x128 for 1.33x the bytes)
-            case 31: return launch_t<ConvTileG<F, 256, 256, 4, 2, 3, false, false, true>>(p, st);
-            case 32: return launch_t<ConvTileG<F, 128, 256, 2, 4, 3, false, false, true>>(p, st);
-            // round 5: deeper rings for the one-part operands (one MFMA product per fragment:
-            // the K loop waits on L2 / HBM latency, so more steps in flight): 256x256 with four
-            // stages (128 KB, three steps in flight) on 32x32x16 / 16x16x32 (five stages exceed the
-            // LDS by the kernel's own 4-byte word)
-            case 38: return launch_t<ConvTileG<F, 256, 256, 4, 2, 4, false, false, true>>(p, st);
-            case 39: return launch_t<ConvTileG<F, 256, 256, 4, 2, 4, true, false, true>>(p, st);
-            // the 16x16x32 forms with fragment prefetch (FP), four and three stages
-            case 40: return launch_t<ConvTileG<F, 256, 256, 4, 2, 4, true, false, true, false,
-                                               true>>(p, st);
-            case 41: return launch_t<ConvTileG<F, 256, 256, 4, 2, 3, true, false, true, false,
-                                               true>>(p, st);
-            default: break;
-        }
-        if (!is_g_tile(id)) return launch_t<ConvTile<F, 128, 64, 2, 2, 1, true>>(p, st);
-        return launch_t<ConvTileG<F, 256, 128, 4, 2, 3, true, false, true>>(p, st);
-    } else {
-    switch (id) {
-        case 0: return launch<F, 128, 128, 2, 2>(p, st);
-        case 1: return launch<F, 64, 128, 2, 2>(p, st);
-        case 2: return launch<F, 32, 256, 1, 4>(p, st);
-        case 3: return launch<F, 128, 64, 2, 2>(p, st);
-        case 4: return launch<F, 64, 64, 2, 2>(p, st);
-        case 5: return launch<F, 256, 128, 4, 2>(p, st);
-        case 6: return launch<F, 256, 128, 4, 2, 2>(p, st);
-        case 7: return launch<F, 128, 128, 2, 2, 2>(p, st);
-        case 8: return launch<F, 128, 64, 2, 2, 2>(p, st);
-        case 9: return launch<F, 64, 64, 2, 2, 2>(p, st);
-        // LDS-DMA pipelined tiles (aligned convolutions only)
-        case 10: return launch_t<ConvTileG<F, 128, 128, 4, 2, 3>>(p, st);
-        case 11: return launch_t<ConvTileG<F, 256, 128, 4, 2, 2>>(p, st);
-        case 12: return launch_t<ConvTileG<F, 128, 128, 2, 2, 3>>(p, st);
-        case 13: return launch_t<ConvTileG<F, 64, 128, 2, 2, 3>>(p, st);
-        // the same LDS-DMA pipelines on the 16x16x32 MFMA
-        case 14: return launch_t<ConvTileG<F, 256, 128, 4, 2, 2, true>>(p, st);
-        case 15: return launch_t<ConvTileG<F, 128, 128, 4, 2, 3, true>>(p, st);
-        case 16: return launch_t<ConvTileG<F, 128, 128, 2, 2, 3, true>>(p, st);
-        // register-staged tiles on the 16x16x32 MFMA
-        case 17: return launch_t<ConvTile<F, 64, 64, 2, 2, 1, true>>(p, st);
-        case 18: return launch_t<ConvTile<F, 128, 64, 2, 2, 1, true>>(p, st);
-        case 19: return launch_t<ConvTile<F, 128, 128, 2, 2, 1, true>>(p, st);
-        case 20: return launch_t<ConvTile<F, 64, 128, 2, 2, 1, true>>(p, st);
-        case 21: return launch_t<ConvTile<F, 32, 256, 1, 4, 1, true>>(p, st);
-        // 256x128 LDS-DMA, 16x16x32, next step's pieces interleaved with the MFMA terms
-        case 22: return launch_t<ConvTileG<F, 256, 128, 4, 2, 2, true, true>>(p, st);
-        // ... with the pieces issued by half of the waves (loader waves)
-        case 23: return launch_t<ConvTileG<F, 256, 128, 4, 2, 2, true, false, true>>(p, st);
-        case 24: return launch_t<ConvTileG<F, 256, 128, 4, 2, 2, true, true, true>>(p, st);
-        case 25: return launch_t<ConvTileG<F, 128, 128, 4, 2, 3, false, false, true>>(p, st);
-        case 26: return launch_t<ConvTileG<F, 128, 128, 4, 2, 3, true, false, true>>(p, st);
-        // ping-pong wave groups (one phase apart: one wave of each SIMD on the MFMA pipe while
-        // the other reads LDS)
-        case 28: return launch_t<ConvTileG<F, 256, 128, 4, 2, 2, true, false, true, true>>(p, st);
-        case 29: return launch_t<ConvTileG<F, 128, 128, 4, 2, 2, true, false, true, true>>(p, st);
-        default: break;
-    }
-    if constexpr (F::NP == 2) {
-        switch (id) {
-            // 256x128 LDS-DMA, 16x16x32, loader waves, THREE stages (147 KB with 2 parts)
-            case 30: return launch_t<ConvTileG<F, 256, 128, 4, 2, 3, true, false, true>>(p, st);
-            // 256x256 LDS-DMA on 32x32x16 (a wave owns 64x128: 1.33x the FLOP per LDS byte of
-            // 256x128), loader waves, two stages (131 KB)
-            case 31: return launch_t<ConvTileG<F, 256, 256, 4, 2, 2, false, false, true>>(p, st);
-            // 128x256 LDS-DMA on 32x32x16, loader waves, three stages (147 KB)
-            case 32: return launch_t<ConvTileG<F, 128, 256, 2, 4, 3, false, false, true>>(p, st);
-            // 256x128 LDS-DMA on 32x32x16, loader waves, three stages
-            case 33: return launch_t<ConvTileG<F, 256, 128, 4, 2, 3, false, false, true>>(p, st);
-            // 128x128 LDS-DMA, 16x16x32, loader waves, TWO stages (64 KB with 2 parts): two
-            // blocks per CU, so one block's epilogue overlaps the other's K loop (the residual
-            // 1x1 layers, whose epilogue traffic otherwise idles the MFMAs of every CU at once)
-            case 34: return launch_t<ConvTileG<F, 128, 128, 4, 2, 2, true, false, true>>(p, st);
-            // tiles 30 / 26 with fragment prefetch (FP): the next step's LDS fragments read
-            // under this step's MFMAs, two steps of LDS-DMA in flight
-            case 35: return launch_t<ConvTileG<F, 256, 128, 4, 2, 3, true, false, true, false,
-                                               true>>(p, st);
-            case 36: return launch_t<ConvTileG<F, 128, 128, 4, 2, 3, true, false, true, false,
-                                               true>>(p, st);
-            // 256x192 LDS-DMA, 16x16x32, loader waves, two stages (115 KB): a launch whose
-            // 192-pixel tiles make exactly one round where 128 makes two and 256 leaves CUs
-            // idle (InceptionV3's SPG heads at 8 x 39^2: 256 tiles on 256 CUs)
-            case 37: return launch_t<ConvTileG<F, 256, 192, 4, 2, 2, true, false, true>>(p, st);
-            default: break;
-        }
-    }
-    return launch_t<ConvTileG<F, 256, 128, 4, 2, 2, true, false, true>>(p, st);
-    }
+    return with_row(resolve(format_of<F>(), id), [&](auto i) {
+        constexpr int I = decltype(i)::value;
+        if constexpr (built<F, I>()) return launch_t<TileAt<F, I>>(p, st);
+        else return TCAM_E_ARG;
+    }, kRows);
 }
-
-// The tiles of a grouped launch (16x16x32 forms: the per-group destinations of their
-// epilogue): 15 / 26 = 128x128 LDS-DMA (26 with loader waves; aligned members only),
-// 17 = 64x64, 18 = 128x64, 20 = 64x128 register-staged.
+// The tiles of a grouped launch are the GROUP rows (16x16x32 forms: the per-group
+// destinations of their epilogue; the LDS-DMA ones for aligned members only); any other id
+// runs the register-staged 128x64 one.
 template <class F>
 int launch_group_tile(int id, ConvX* ps, int n, hipStream_t st) {
-    switch (id) {
-        case 15: return launch_group_t<ConvTileG<F, 128, 128, 4, 2, 3, true>>(ps, n, st);
-        case 26: return launch_group_t<ConvTileG<F, 128, 128, 4, 2, 3, true, false, true>>(ps, n, st);
-        case 17: return launch_group_t<ConvTile<F, 64, 64, 2, 2, 1, true>>(ps, n, st);
-        case 20: return launch_group_t<ConvTile<F, 64, 128, 2, 2, 1, true>>(ps, n, st);
-        default: return launch_group_t<ConvTile<F, 128, 64, 2, 2, 1, true>>(ps, n, st);
-    }
+    const int row = find_row(bit(format_of<F>()), is_group_tile(id) ? id : T_REG_128x64_M16);
+    return with_row(row, [&](auto i) {
+        constexpr int I = decltype(i)::value;
+        if constexpr (built<F, I>(GROUP)) return launch_group_t<TileAt<F, I>>(ps, n, st);
+        else return TCAM_E_ARG;
+    }, kRows);
 }
-bool is_group_tile(int id) { return id == 15 || id == 26 || id == 17 || id == 18 || id == 20; }
+int g_force_tile = -1;
 
 // Per-shape choice from scripts/tune_conv_x6.py on MI355X (ResNet50-TCAM,
 // batch 32, profiles/round1_tune_x6*.txt).  `aligned`: every source C % 32 == 0
 // (the LDS-DMA tiles need it).
-bool is_g_tile(int id) { return (id >= 10 && id <= 16) || (id >= 22 && id <= 26) || id >= 28; }
-bool is_f16_only_tile(int id) { return id >= 30; }
-// tiles on v_mfma_f32_16x16x32_bf16 (epilogue16)
-bool is_m16_tile(int id) { return (id >= 14 && id <= 24) || id == 26 || (id >= 28 && id <= 30) || (id >= 34 && id <= 37) || id >= 39; }
-
 int choose_tile_x6(const ConvX& p, bool aligned) {
     // 16x16x32-MFMA forms where they measured ahead (profiles/round1_tune_x6_m16*.txt: the
     // 256x128 LDS-DMA tile +0-4 % on deep-K layers, the register-staged 128x64 +3-13 % on
@@ -2492,31 +2547,32 @@ int choose_tile_x6(const ConvX& p, bool aligned) {
     const long ntn = (p.N + 127) / 128;
     const bool deep = p.K >= 32 * 32 && g_force_sk != 0;
     if (aligned && p.Cout >= 256 && p.K >= 1024) {
-        if (deep && (long)((p.Cout + 255) / 256) * ntn * 2 < 256) return 6;
-        return (nolw & 1) ? (tap3 ? 22 : 14) : 23;
+        if (deep && (long)((p.Cout + 255) / 256) * ntn * 2 < 256) return T_REG_256x128_S2;
+        return (nolw & 1) ? (tap3 ? T_DMA_256x128_M16_IL : T_DMA_256x128_M16)
+                          : T_DMA_256x128_M16_LW;
     }
-    if (aligned && p.Cout >= 2048 && p.K >= 512) return (nolw & 1) ? 14 : 23;  // layer4 c3
+    if (aligned && p.Cout >= 2048 && p.K >= 512)                                  // layer4 c3
+        return (nolw & 1) ? T_DMA_256x128_M16 : T_DMA_256x128_M16_LW;
     // 128x128 LDS-DMA: 3x3 on 16x16x32 with loader waves (+10 %), 1x1 on 16x16x32 (+10 %
     // over the 32x32x16 form since the LDS-staged epilogue, profiles/round2_tune_x6_epi.txt)
     if (aligned && p.Cout == 128) {
-        if (deep && tap3 && ntn * 2 < 256) return 3;
-        return tap3 ? ((nolw & 2) ? 10 : 26) : 15;
+        if (deep && tap3 && ntn * 2 < 256) return T_REG_128x64;
+        return tap3 ? ((nolw & 2) ? T_DMA_128x128 : T_DMA_128x128_M16_LW) : T_DMA_128x128_M16;
     }
     // Cout between 128 and 256 (InceptionV3's 160 / 192-channel 1x7 / 7x1 / 1x1 convs): the
     // 128x128 LDS-DMA tiles (+28 % on the 1x7 / 7x1 layers, +14 % on the 1x1, over the
     // register-staged 128x64)
-    if (aligned && p.Cout > 128 && p.Cout < 256) return tap3 ? 26 : 15;
-    if (p.Cout >= 512 && p.K <= 128) return 17;              // l2.c3: 64x64 (+6 %)
-    if (p.Cout >= 256) return 18;                             // wide 1x1 (c3) layers
-    if (p.Cout >= 128) return 3;
-    if (p.Cout == 64) return p.K >= 2048 ? 20 : 17;
-    if (p.Cout >= 32) return 17;
-    return 2;
+    if (aligned && p.Cout > 128 && p.Cout < 256)
+        return tap3 ? T_DMA_128x128_M16_LW : T_DMA_128x128_M16;
+    if (p.Cout >= 512 && p.K <= 128) return T_REG_64x64_M16;  // l2.c3: 64x64 (+6 %)
+    if (p.Cout >= 256) return T_REG_128x64_M16;               // wide 1x1 (c3) layers
+    if (p.Cout >= 128) return T_REG_128x64;
+    if (p.Cout == 64) return p.K >= 2048 ? T_REG_64x128_M16 : T_REG_64x64_M16;
+    if (p.Cout >= 32) return T_REG_64x64_M16;
+    return T_REG_32x256;
 }
 
-// FmtF16: the 2-part stages leave LDS for a THIRD stage of the 256x128 loader-wave tile:
-// +5-17 % on the deep-K layers over the two-stage tile (d0.c1 332 -> 391 TF, l4.c3ds
-// 297 -> 345, l4.c3 208 -> 230; profiles/round3_tune_f16.txt)
+// CUs of the device (256, the MI355X's, when there is none: the host-only plan query)
 int num_cus() {
     static int cus = [] {
         int dev = 0, n = 0;
@@ -2572,14 +2628,16 @@ int fp_tile(int id, const ConvX& p) {
         return e ? atoi(e) : 1;
     }();
     if (!on || (on == 1 && p.KH * p.KW == 1)) return id;
-    return id == 30 ? 35 : (id == 26 ? 36 : id);
+    return id == T_DMA_256x128_S3_M16_LW ? T_DMA_256x128_S3_M16_LW_FP
+           : id == T_DMA_128x128_M16_LW  ? T_DMA_128x128_M16_LW_FP : id;
 }
 
-int choose_tile(ConvX& p, bool aligned, int fmt) {
+int choose_tile(ConvX& p, bool aligned, Format fmt) {
     const int mid = mapped_tile(p);
     if (mid >= 0) return mid;
     const int id = choose_tile_x6(p, aligned);
-    if (fmt == 2 && aligned && (id == 23 || id == 14 || id == 6)) {
+    const bool dma256 = id == T_DMA_256x128_M16_LW || id == T_DMA_256x128_M16;
+    if (fmt == Format::H1 && aligned && (dma256 || id == T_REG_256x128_S2)) {
         // FmtH1 (AMP, one fp16 product per K-step): the 256x128 tile is bound by its L2 bytes
         // per FLOP; the 256x256 tile moves 2/3 of them.  One 256x256 tile costs ~1.55 of a
         // 256x128 one (both one block per CU), so it wins when it saves whole rounds of
@@ -2594,9 +2652,10 @@ int choose_tile(ConvX& p, bool aligned, int fmt) {
         // +3-6 % (profiles/round5_ab_amp_fp.txt); l4.c3 (K = 512, 16 steps) stays on 31.
         // TCAM_AMP_FP=0 for A/B.
         static const int amp_fp = getenv("TCAM_AMP_FP") ? atoi(getenv("TCAM_AMP_FP")) : 1;
-        if (r256 * 155 < r128 * 100) return amp_fp && p.K >= 1024 ? 41 : 31;
+        if (r256 * 155 < r128 * 100)
+            return amp_fp && p.K >= 1024 ? T_DMA_256x256_S3_M16_LW_FP : T_DMA_256x256_LW;
     }
-    if (fmt == 1 && aligned && (id == 23 || id == 14) && p.Cout >= 1024 && p.K >= 4096) {
+    if (fmt == Format::F16 && aligned && dma256 && p.Cout >= 1024 && p.K >= 4096) {
         // FmtF16: a wide, deep launch whose 256x128 tiles take two rounds and whose 256x256
         // tiles fit in one (InceptionV3's SPG heads on an 8-frame 299^2 shard: 344 -> 172
         // tiles) runs on 256x256: +1.5 % family frames/s (profiles/round4_ab_family_heads.txt).
@@ -2611,25 +2670,30 @@ int choose_tile(ConvX& p, bool aligned, int fmt) {
         // InceptionV3 (its two-stage ring hides less latency than the three-stage 256x128 /
         // 256x256 rings): off by default, TCAM_CONV_T192=1 to A/B (profiles/round5_ab_t192.txt)
         static const int t192 = getenv("TCAM_CONV_T192") ? atoi(getenv("TCAM_CONV_T192")) : 0;
-        if (t192 && r192 * 192 < r128 * 128 && r192 * 192 < r256 * 256) return 37;
-        if (r256 == 1 && r128 == 2) return 31;
+        if (t192 && r192 * 192 < r128 * 128 && r192 * 192 < r256 * 256)
+            return T_DMA_256x192_M16_LW;
+        if (r256 == 1 && r128 == 2) return T_DMA_256x256_LW;
     }
-    if (fmt == 1 && id == 6) {
+    if (fmt == Format::F16 && id == T_REG_256x128_S2) {
         // FmtF16, an under-filled deep launch (fewer 128x128 tiles than CUs; x6 takes the
         // register-staged stream-K tile there): the 128x128 LDS-DMA tile without stream-K.
         // InceptionV3's decoder block 0 (96 tiles of 256x128 on an 8-frame shard): family
         // 2139-2150 -> 2212-2216 frames/s, against 2119-2122 for a stream-K grid of 256 and
         // 2085-2087 for the register-staged 128x64 (profiles/round4_ab_family_d0.txt)
-        return p.KH * p.KW > 1 ? fp_tile(26, p) : 15;
+        return p.KH * p.KW > 1 ? fp_tile(T_DMA_128x128_M16_LW, p) : T_DMA_128x128_M16;
     }
-    if (fmt == 1 && id == 3 && aligned && p.Cout == 128 && p.KH * p.KW > 1) {
+    if (fmt == Format::F16 && id == T_REG_128x64 && aligned && p.Cout == 128 &&
+        p.KH * p.KW > 1) {
         // likewise for an under-filled deep 128-channel 3x3 launch (InceptionV3 decoder
         // blocks 1-2): 128x128 LDS-DMA, frac 0.289-0.296 -> 0.297-0.299 in three rounds
         // (profiles/round4_ab_family_c128.txt)
-        return fp_tile(26, p);
+        return fp_tile(T_DMA_128x128_M16_LW, p);
     }
-    if (fmt && (id == 23 || id == 14)) return fp_tile(30, p);
-    if (fmt == 1 && id == 26) return fp_tile(26, p);
+    // FmtF16: the 2-part stages leave LDS for a THIRD stage of the 256x128 loader-wave tile:
+    // +5-17 % on the deep-K layers over the two-stage tile (d0.c1 332 -> 391 TF, l4.c3ds
+    // 297 -> 345, l4.c3 208 -> 230; profiles/round3_tune_f16.txt)
+    if (fmt != Format::X6 && dma256) return fp_tile(T_DMA_256x128_S3_M16_LW, p);
+    if (fmt == Format::F16 && id == T_DMA_128x128_M16_LW) return fp_tile(id, p);
     return id;
 }
 
@@ -2667,96 +2731,6 @@ extern "C" int tcam_conv_x6_debug(int flags) {
 extern "C" int tcam_conv_x6_force_streamk(int grid) {
     g_force_sk = grid;
     return TCAM_OK;
-}
-
-// one output tensor of a (possibly grouped) launch: channels [c_begin, next c_begin) of
-// the conv go to channels [coff, ...) of `ptr`, a tensor of cstride channels per pixel
-struct Dst {
-    void* ptr;
-    int c_begin, cstride, coff;
-};
-
-// fmt 0: FmtX6 (S3 operands), 1: FmtF16 (S2 operands, wscale + oflow), 2: FmtH1 (S1),
-// 3: FmtF16S3 (S2 operands + wscale, S3 output: the f16x3 data gradient)
-struct Fmt {
-    int fmt;
-    const float* wscale;
-    int* oflow;
-    int eb() const { return fmt == 2 ? 2 : fmt ? 4 : 6; }   // input bytes per element
-    int eb_out() const { return fmt == 3 ? 6 : eb(); }      // output bytes per element
-};
-
-static int conv2d_x6_launch(const tcam_conv_src* srcs, int nsrc, int B, const void* wt,
-                            const float* bias, const void* residual, const Dst* dst, int nd,
-                            int Cout, int Hout, int Wout, int KH, int KW, int pad_h, int pad_w,
-                            int relu, void* ws, size_t ws_bytes, void* stream, Fmt f);
-static int build_convx(ConvX& p, bool& aligned, const tcam_conv_src* srcs, int nsrc, int B,
-                       const void* wt, const float* bias, const void* residual, const Dst* dst,
-                       int nd, int Cout, int Hout, int Wout, int KH, int KW, int pad_h, int pad_w,
-                       int relu, void* ws, size_t ws_bytes, Fmt f);
-
-// Buffer offsets inside the kernel are 32-bit: batches whose tensors exceed 2 GiB run as
-// consecutive launches over frame chunks (per-frame convolution: exact).
-static int conv2d_x6_chunked(const tcam_conv_src* srcs, int nsrc, int B, const void* wt,
-                             const float* bias, const void* residual, const Dst* dst, int nd,
-                             int Cout, int Hout, int Wout, int KH, int KW, int pad_h, int pad_w,
-                             int relu, void* ws, size_t ws_bytes, void* stream, Fmt f) {
-    TCAM_REQUIRE(srcs && (nsrc == 1 || nsrc == 2) && B > 0 && Cout > 0 && nd >= 1 && nd <= 3);
-    const int eb = f.eb(), ebo = f.eb_out();
-    long per = (long)Hout * Wout * Cout * ebo;   // bytes per frame, largest tensor
-    for (int i = 0; i < nd; ++i) {
-        TCAM_REQUIRE(dst[i].cstride > 0);
-        per = std::max(per, (long)Hout * Wout * dst[i].cstride * ebo);
-    }
-    for (int i = 0; i < nsrc; ++i)
-        per = std::max(per, (long)srcs[i].H * srcs[i].W * srcs[i].C * eb);
-    const long lim = (long)OOB - (1l << 20);
-    if (per * B < lim)
-        return conv2d_x6_launch(srcs, nsrc, B, wt, bias, residual, dst, nd, Cout, Hout, Wout,
-                                KH, KW, pad_h, pad_w, relu, ws, ws_bytes, stream, f);
-    const int fc = (int)std::max(1l, lim / per);
-    for (int b0 = 0; b0 < B; b0 += fc) {
-        const int nb = std::min(fc, B - b0);
-        tcam_conv_src sub[2];
-        for (int i = 0; i < nsrc; ++i) {
-            sub[i] = srcs[i];
-            sub[i].ptr = (const float*)((const char*)srcs[i].ptr +
-                                        (long)b0 * srcs[i].H * srcs[i].W * srcs[i].C * eb);
-        }
-        const long ofr = (long)b0 * Hout * Wout;
-        Dst sd[3];
-        for (int i = 0; i < nd; ++i) {
-            sd[i] = dst[i];
-            sd[i].ptr = (void*)((char*)dst[i].ptr + ofr * dst[i].cstride * ebo);
-        }
-        const int rc = conv2d_x6_launch(
-            sub, nsrc, nb, wt, bias,
-            residual ? (const void*)((const char*)residual + ofr * Cout * ebo) : nullptr, sd, nd,
-            Cout, Hout, Wout, KH, KW, pad_h, pad_w, relu, ws, ws_bytes, stream, f);
-        if (rc != TCAM_OK) return rc;
-    }
-    return TCAM_OK;
-}
-
-extern "C" int tcam_conv2d_x6(const tcam_conv_src* srcs, int nsrc, int B, const void* wt,
-                              const float* bias, const void* residual, void* out, int Cout,
-                              int Hout, int Wout, int KH, int KW, int pad_h, int pad_w, int relu,
-                              int out_cstride, int out_coff, void* ws, size_t ws_bytes,
-                              void* stream) {
-    const Dst d{out, 0, out_cstride ? out_cstride : Cout, out_coff};
-    return conv2d_x6_chunked(srcs, nsrc, B, wt, bias, residual, &d, 1, Cout, Hout, Wout, KH, KW,
-                             pad_h, pad_w, relu, ws, ws_bytes, stream, Fmt{0, nullptr, nullptr});
-}
-
-extern "C" int tcam_conv2d_f16x3(const tcam_conv_src* srcs, int nsrc, int B, const void* wt,
-                                 const float* wscale, const float* bias, const void* residual,
-                                 void* out, int Cout, int Hout, int Wout, int KH, int KW,
-                                 int pad_h, int pad_w, int relu, int out_cstride, int out_coff,
-                                 int* oflow, void* ws, size_t ws_bytes, void* stream) {
-    TCAM_REQUIRE(wscale && ((uintptr_t)wscale & 15) == 0);
-    const Dst d{out, 0, out_cstride ? out_cstride : Cout, out_coff};
-    return conv2d_x6_chunked(srcs, nsrc, B, wt, bias, residual, &d, 1, Cout, Hout, Wout, KH, KW,
-                             pad_h, pad_w, relu, ws, ws_bytes, stream, Fmt{1, wscale, oflow});
 }
 
 static unsigned long long* g_bneck_dbg = nullptr;
@@ -2855,91 +2829,21 @@ extern "C" int tcam_bottleneck_f16(const void* x, int B, int H, int W, int cin, 
                                     nullptr, b3, ds, out, nullptr, stream);
 }
 
-extern "C" int tcam_conv2d_f16x3_s3out(const tcam_conv_src* srcs, int nsrc, int B,
-                                       const void* wt, const float* wscale, const float* bias,
-                                       void* out, int Cout, int Hout, int Wout, int KH, int KW,
-                                       int pad_h, int pad_w, int relu, int out_cstride,
-                                       int out_coff, void* ws, size_t ws_bytes, void* stream) {
-    TCAM_REQUIRE(wscale && ((uintptr_t)wscale & 15) == 0);
-    const Dst d{out, 0, out_cstride ? out_cstride : Cout, out_coff};
-    return conv2d_x6_chunked(srcs, nsrc, B, wt, bias, nullptr, &d, 1, Cout, Hout, Wout, KH, KW,
-                             pad_h, pad_w, relu, ws, ws_bytes, stream, Fmt{3, wscale, nullptr});
-}
+// one output tensor of a (possibly grouped) launch: channels [c_begin, next c_begin) of
+// the conv go to channels [coff, ...) of `ptr`, a tensor of cstride channels per pixel
+struct Dst {
+    void* ptr;
+    int c_begin, cstride, coff;
+};
 
-extern "C" int tcam_conv2d_f16(const tcam_conv_src* srcs, int nsrc, int B, const void* wt,
-                               const float* bias, const void* residual, void* out, int Cout,
-                               int Hout, int Wout, int KH, int KW, int pad_h, int pad_w, int relu,
-                               int out_cstride, int out_coff, void* ws, size_t ws_bytes,
-                               void* stream) {
-    const Dst d{out, 0, out_cstride ? out_cstride : Cout, out_coff};
-    return conv2d_x6_chunked(srcs, nsrc, B, wt, bias, residual, &d, 1, Cout, Hout, Wout, KH, KW,
-                             pad_h, pad_w, relu, ws, ws_bytes, stream, Fmt{2, nullptr, nullptr});
-}
-
-extern "C" int tcam_conv2d_x6_multi(const tcam_conv_src* srcs, int nsrc, int B, const void* wt,
-                                    const float* bias, int Cout, int Hout, int Wout, int KH,
-                                    int KW, int pad_h, int pad_w, int relu,
-                                    const tcam_conv_dst* dst, int ndst, void* ws,
-                                    size_t ws_bytes, void* stream) {
-    TCAM_REQUIRE(dst && ndst >= 1 && ndst <= 3 && dst[0].c_begin == 0);
-    Dst d[3];
-    for (int i = 0; i < ndst; ++i) {
-        const int c1 = i + 1 < ndst ? dst[i + 1].c_begin : Cout;
-        TCAM_REQUIRE(dst[i].ptr && dst[i].c_begin % 8 == 0 && c1 > dst[i].c_begin);
-        d[i] = Dst{dst[i].ptr, dst[i].c_begin, dst[i].cstride, dst[i].coff};
-    }
-    return conv2d_x6_chunked(srcs, nsrc, B, wt, bias, nullptr, d, ndst, Cout, Hout, Wout, KH,
-                             KW, pad_h, pad_w, relu, ws, ws_bytes, stream, Fmt{0, nullptr, nullptr});
-}
-
-extern "C" int tcam_conv2d_f16x3_multi(const tcam_conv_src* srcs, int nsrc, int B, const void* wt,
-                                       const float* wscale, const float* bias, int Cout,
-                                       int Hout, int Wout, int KH, int KW, int pad_h, int pad_w,
-                                       int relu, const tcam_conv_dst* dst, int ndst, int* oflow,
-                                       void* ws, size_t ws_bytes, void* stream) {
-    TCAM_REQUIRE(wscale && ((uintptr_t)wscale & 15) == 0);
-    TCAM_REQUIRE(dst && ndst >= 1 && ndst <= 3 && dst[0].c_begin == 0);
-    Dst d[3];
-    for (int i = 0; i < ndst; ++i) {
-        const int c1 = i + 1 < ndst ? dst[i + 1].c_begin : Cout;
-        TCAM_REQUIRE(dst[i].ptr && dst[i].c_begin % 8 == 0 && c1 > dst[i].c_begin);
-        d[i] = Dst{dst[i].ptr, dst[i].c_begin, dst[i].cstride, dst[i].coff};
-    }
-    return conv2d_x6_chunked(srcs, nsrc, B, wt, bias, nullptr, d, ndst, Cout, Hout, Wout, KH,
-                             KW, pad_h, pad_w, relu, ws, ws_bytes, stream, Fmt{1, wscale, oflow});
-}
-
-extern "C" int tcam_conv2d_group(const tcam_conv_prob* probs, int nprob, int B, int fmt,
-                                 int tile, int* oflow, void* stream) {
-    TCAM_REQUIRE(probs && nprob >= 1 && nprob <= kMaxGroup && (fmt == 0 || fmt == 1));
-    TCAM_REQUIRE(tile == -1 || is_group_tile(tile));
-    const Fmt f{fmt, nullptr, fmt ? oflow : nullptr};
-    ConvX ps[kMaxGroup];
-    bool all_aligned = true, taps = false;
-    for (int i = 0; i < nprob; ++i) {
-        const tcam_conv_prob& q = probs[i];
-        Fmt fi = f;
-        if (fmt) {
-            TCAM_REQUIRE(q.wscale && ((uintptr_t)q.wscale & 15) == 0);
-            fi.wscale = q.wscale;
-        } else {
-            TCAM_REQUIRE(!q.wscale);
-        }
-        const Dst d{q.out, 0, q.out_cstride ? q.out_cstride : q.Cout, q.out_coff};
-        bool aligned;
-        const int rc = build_convx(ps[i], aligned, &q.src, 1, B, q.wt, q.bias, nullptr, &d, 1,
-                                   q.Cout, q.Hout, q.Wout, q.KH, q.KW, q.pad_h, q.pad_w, q.relu,
-                                   nullptr, 0, fi);
-        if (rc != TCAM_OK) return rc;
-        all_aligned = all_aligned && aligned;
-        taps = taps || q.KH * q.KW > 1;
-    }
-    int id = g_force_tile >= 0 && is_group_tile(g_force_tile) ? g_force_tile : tile;
-    if (id < 0) id = all_aligned ? (taps ? 26 : 15) : 18;
-    if ((id == 15 || id == 26) && !all_aligned) id = 18;
-    return fmt ? launch_group_tile<FmtF16>(id, ps, nprob, as_stream(stream))
-               : launch_group_tile<FmtX6>(id, ps, nprob, as_stream(stream));
-}
+struct Fmt {
+    Format fmt;
+    const float* wscale;
+    int* oflow;
+    // input bytes per element
+    int eb() const { return fmt == Format::H1 ? 2 : fmt == Format::X6 ? 6 : 4; }
+    int eb_out() const { return fmt == Format::F16S3 ? 6 : eb(); }  // output bytes per element
+};
 
 // The kernel parameters of one convolution (every check of the entry points); `aligned`:
 // every source C % 32 == 0 (the LDS-DMA tiles need it).
@@ -3041,6 +2945,24 @@ static int build_convx(ConvX& p, bool& aligned, const tcam_conv_src* srcs, int n
     return TCAM_OK;
 }
 
+// The tile one launch of `p` runs right now (the forced id and stream-K state included):
+// kThinTile = conv3x3_thin_kernel, else an id for launch_tile.
+static int plan_tile(ConvX& p, bool aligned, const tcam_conv_src* srcs, int nsrc, int nd,
+                     bool has_res, Format fmt) {
+    // thin 3x3 layers: the halo-tiled kernel (tile id kThinTile when forced)
+    if ((g_force_tile < 0 || g_force_tile == kThinTile) && nd == 1 &&
+        thin_ok(p, srcs, nsrc, has_res))
+        return kThinTile;
+    int id = (g_force_tile >= 0 && g_force_tile < kNumTiles && g_force_tile != kThinTile)
+                 ? g_force_tile : choose_tile(p, aligned, fmt);
+    if (is_g_tile(id) && !aligned) id = choose_tile(p, false, fmt);
+    if (is_f16_only_tile(id) && fmt == Format::X6) id = choose_tile(p, aligned, Format::X6);
+    // a multi-destination launch needs the 16x16x32 tiles' epilogue (per-group destinations)
+    if (nd > 1 && !is_m16_tile(fmt, id)) id = aligned ? T_DMA_128x128_M16 : T_REG_128x64_M16;
+    // (a TCAM_CONV_TILE_MAP entry may name kThinTile: that is no launch_tile id)
+    return id == kThinTile ? kTiles[resolve(fmt, id)].id : id;
+}
+
 static int conv2d_x6_launch(const tcam_conv_src* srcs, int nsrc, int B, const void* wt,
                             const float* bias, const void* residual, const Dst* dst, int nd,
                             int Cout, int Hout, int Wout, int KH, int KW, int pad_h, int pad_w,
@@ -3050,29 +2972,215 @@ static int conv2d_x6_launch(const tcam_conv_src* srcs, int nsrc, int B, const vo
     const int rc = build_convx(p, aligned, srcs, nsrc, B, wt, bias, residual, dst, nd, Cout, Hout,
                                Wout, KH, KW, pad_h, pad_w, relu, ws, ws_bytes, f);
     if (rc != TCAM_OK) return rc;
-    // thin 3x3 layers: the halo-tiled kernel (tile id kThinTile when forced)
-    if ((g_force_tile < 0 || g_force_tile == kThinTile) && nd == 1 &&
-        thin_ok(p, srcs, nsrc, residual)) {
-        const long blocks = (long)B * ((Hout + TH_T - 1) / TH_T) * ((Wout + TH_T - 1) / TH_T);
-        if (f.fmt == 2) launch_thin<FmtH1>(p, blocks, Cout, as_stream(stream));
-        else if (f.fmt == 3) launch_thin<FmtF16S3>(p, blocks, Cout, as_stream(stream));
-        else if (f.fmt) launch_thin<FmtF16>(p, blocks, Cout, as_stream(stream));
-        else launch_thin<FmtX6>(p, blocks, Cout, as_stream(stream));
-        TCAM_CHECK_LAUNCH();
-        return TCAM_OK;
-    }
-    int id = (g_force_tile >= 0 && g_force_tile < kNumTiles && g_force_tile != kThinTile)
-                 ? g_force_tile : choose_tile(p, aligned, f.fmt);
-    if (is_g_tile(id) && !aligned) id = choose_tile(p, false, f.fmt);
-    if (is_f16_only_tile(id) && !f.fmt) id = choose_tile(p, aligned, 0);
-    // a grouped launch needs the 16x16x32 tiles' epilogue (per-group destinations)
-    if (nd > 1 && !is_m16_tile(id)) id = aligned ? 15 : 18;
+    const int id = plan_tile(p, aligned, srcs, nsrc, nd, residual != nullptr, f.fmt);
     // l4.c3 (205 MB of residual): 0.235 -> 0.219 ms with non-temporal residual reads on its
     // 256x128 LDS-DMA tile; the register-staged tiles (l3.c3) measured slower with them
     // (profiles/round4_ab_nt_residual.txt)
     p.ntres = is_g_tile(id) ? 1 : 0;
-    if (f.fmt == 2) return launch_tile<FmtH1>(id, p, as_stream(stream));
-    if (f.fmt == 3) return launch_tile<FmtF16S3>(id, p, as_stream(stream));
-    return f.fmt ? launch_tile<FmtF16>(id, p, as_stream(stream))
-                 : launch_tile<FmtX6>(id, p, as_stream(stream));
+    return with_format(f.fmt, [&](auto F) {
+        using FT = decltype(F);
+        if (id != kThinTile) return launch_tile<FT>(id, p, as_stream(stream));
+        const long blocks = (long)B * ((Hout + TH_T - 1) / TH_T) * ((Wout + TH_T - 1) / TH_T);
+        launch_thin<FT>(p, blocks, Cout, as_stream(stream));
+        TCAM_CHECK_LAUNCH();
+        return TCAM_OK;
+    });
+}
+
+// Buffer offsets inside the kernel are 32-bit: batches whose tensors exceed 2 GiB run as
+// consecutive launches over frame chunks (per-frame convolution: exact).  Frames per launch:
+static int chunk_frames(const tcam_conv_src* srcs, int nsrc, int B, const Dst* dst, int nd,
+                        int Cout, int Hout, int Wout, Fmt f) {
+    const int eb = f.eb(), ebo = f.eb_out();
+    long per = (long)Hout * Wout * Cout * ebo;   // bytes per frame, largest tensor
+    for (int i = 0; i < nd; ++i) per = std::max(per, (long)Hout * Wout * dst[i].cstride * ebo);
+    for (int i = 0; i < nsrc; ++i)
+        per = std::max(per, (long)srcs[i].H * srcs[i].W * srcs[i].C * eb);
+    const long lim = (long)OOB - (1l << 20);
+    return per * B < lim ? B : (int)std::max(1l, lim / per);
+}
+
+static int conv2d_x6_chunked(const tcam_conv_src* srcs, int nsrc, int B, const void* wt,
+                             const float* bias, const void* residual, const Dst* dst, int nd,
+                             int Cout, int Hout, int Wout, int KH, int KW, int pad_h, int pad_w,
+                             int relu, void* ws, size_t ws_bytes, void* stream, Fmt f) {
+    TCAM_REQUIRE(srcs && (nsrc == 1 || nsrc == 2) && B > 0 && Cout > 0 && nd >= 1 && nd <= 3);
+    for (int i = 0; i < nd; ++i) TCAM_REQUIRE(dst[i].cstride > 0);
+    const int eb = f.eb(), ebo = f.eb_out();
+    const int fc = chunk_frames(srcs, nsrc, B, dst, nd, Cout, Hout, Wout, f);
+    for (int b0 = 0; b0 < B; b0 += fc) {
+        const int nb = std::min(fc, B - b0);
+        tcam_conv_src sub[2];
+        for (int i = 0; i < nsrc; ++i) {
+            sub[i] = srcs[i];
+            sub[i].ptr = (const float*)((const char*)srcs[i].ptr +
+                                        (long)b0 * srcs[i].H * srcs[i].W * srcs[i].C * eb);
+        }
+        const long ofr = (long)b0 * Hout * Wout;
+        Dst sd[3];
+        for (int i = 0; i < nd; ++i) {
+            sd[i] = dst[i];
+            sd[i].ptr = (void*)((char*)dst[i].ptr + ofr * dst[i].cstride * ebo);
+        }
+        const int rc = conv2d_x6_launch(
+            sub, nsrc, nb, wt, bias,
+            residual ? (const void*)((const char*)residual + ofr * Cout * ebo) : nullptr, sd, nd,
+            Cout, Hout, Wout, KH, KW, pad_h, pad_w, relu, ws, ws_bytes, stream, f);
+        if (rc != TCAM_OK) return rc;
+    }
+    return TCAM_OK;
+}
+
+extern "C" int tcam_conv2d_x6(const tcam_conv_src* srcs, int nsrc, int B, const void* wt,
+                              const float* bias, const void* residual, void* out, int Cout,
+                              int Hout, int Wout, int KH, int KW, int pad_h, int pad_w, int relu,
+                              int out_cstride, int out_coff, void* ws, size_t ws_bytes,
+                              void* stream) {
+    const Dst d{out, 0, out_cstride ? out_cstride : Cout, out_coff};
+    return conv2d_x6_chunked(srcs, nsrc, B, wt, bias, residual, &d, 1, Cout, Hout, Wout, KH, KW,
+                             pad_h, pad_w, relu, ws, ws_bytes, stream,
+                             Fmt{Format::X6, nullptr, nullptr});
+}
+
+extern "C" int tcam_conv2d_f16x3(const tcam_conv_src* srcs, int nsrc, int B, const void* wt,
+                                 const float* wscale, const float* bias, const void* residual,
+                                 void* out, int Cout, int Hout, int Wout, int KH, int KW,
+                                 int pad_h, int pad_w, int relu, int out_cstride, int out_coff,
+                                 int* oflow, void* ws, size_t ws_bytes, void* stream) {
+    TCAM_REQUIRE(wscale && ((uintptr_t)wscale & 15) == 0);
+    const Dst d{out, 0, out_cstride ? out_cstride : Cout, out_coff};
+    return conv2d_x6_chunked(srcs, nsrc, B, wt, bias, residual, &d, 1, Cout, Hout, Wout, KH, KW,
+                             pad_h, pad_w, relu, ws, ws_bytes, stream,
+                             Fmt{Format::F16, wscale, oflow});
+}
+
+extern "C" int tcam_conv2d_f16x3_s3out(const tcam_conv_src* srcs, int nsrc, int B,
+                                       const void* wt, const float* wscale, const float* bias,
+                                       void* out, int Cout, int Hout, int Wout, int KH, int KW,
+                                       int pad_h, int pad_w, int relu, int out_cstride,
+                                       int out_coff, void* ws, size_t ws_bytes, void* stream) {
+    TCAM_REQUIRE(wscale && ((uintptr_t)wscale & 15) == 0);
+    const Dst d{out, 0, out_cstride ? out_cstride : Cout, out_coff};
+    return conv2d_x6_chunked(srcs, nsrc, B, wt, bias, nullptr, &d, 1, Cout, Hout, Wout, KH, KW,
+                             pad_h, pad_w, relu, ws, ws_bytes, stream,
+                             Fmt{Format::F16S3, wscale, nullptr});
+}
+
+extern "C" int tcam_conv2d_f16(const tcam_conv_src* srcs, int nsrc, int B, const void* wt,
+                               const float* bias, const void* residual, void* out, int Cout,
+                               int Hout, int Wout, int KH, int KW, int pad_h, int pad_w, int relu,
+                               int out_cstride, int out_coff, void* ws, size_t ws_bytes,
+                               void* stream) {
+    const Dst d{out, 0, out_cstride ? out_cstride : Cout, out_coff};
+    return conv2d_x6_chunked(srcs, nsrc, B, wt, bias, residual, &d, 1, Cout, Hout, Wout, KH, KW,
+                             pad_h, pad_w, relu, ws, ws_bytes, stream,
+                             Fmt{Format::H1, nullptr, nullptr});
+}
+
+// the Dst list of a multi-destination entry point
+static int multi_dsts(Dst (&d)[3], const tcam_conv_dst* dst, int ndst, int Cout) {
+    TCAM_REQUIRE(dst && ndst >= 1 && ndst <= 3 && dst[0].c_begin == 0);
+    for (int i = 0; i < ndst; ++i) {
+        const int c1 = i + 1 < ndst ? dst[i + 1].c_begin : Cout;
+        TCAM_REQUIRE(dst[i].ptr && dst[i].c_begin % 8 == 0 && c1 > dst[i].c_begin);
+        d[i] = Dst{dst[i].ptr, dst[i].c_begin, dst[i].cstride, dst[i].coff};
+    }
+    return TCAM_OK;
+}
+
+extern "C" int tcam_conv2d_x6_multi(const tcam_conv_src* srcs, int nsrc, int B, const void* wt,
+                                    const float* bias, int Cout, int Hout, int Wout, int KH,
+                                    int KW, int pad_h, int pad_w, int relu,
+                                    const tcam_conv_dst* dst, int ndst, void* ws,
+                                    size_t ws_bytes, void* stream) {
+    Dst d[3];
+    const int rc = multi_dsts(d, dst, ndst, Cout);
+    if (rc != TCAM_OK) return rc;
+    return conv2d_x6_chunked(srcs, nsrc, B, wt, bias, nullptr, d, ndst, Cout, Hout, Wout, KH,
+                             KW, pad_h, pad_w, relu, ws, ws_bytes, stream,
+                             Fmt{Format::X6, nullptr, nullptr});
+}
+
+extern "C" int tcam_conv2d_f16x3_multi(const tcam_conv_src* srcs, int nsrc, int B, const void* wt,
+                                       const float* wscale, const float* bias, int Cout,
+                                       int Hout, int Wout, int KH, int KW, int pad_h, int pad_w,
+                                       int relu, const tcam_conv_dst* dst, int ndst, int* oflow,
+                                       void* ws, size_t ws_bytes, void* stream) {
+    TCAM_REQUIRE(wscale && ((uintptr_t)wscale & 15) == 0);
+    Dst d[3];
+    const int rc = multi_dsts(d, dst, ndst, Cout);
+    if (rc != TCAM_OK) return rc;
+    return conv2d_x6_chunked(srcs, nsrc, B, wt, bias, nullptr, d, ndst, Cout, Hout, Wout, KH,
+                             KW, pad_h, pad_w, relu, ws, ws_bytes, stream,
+                             Fmt{Format::F16, wscale, oflow});
+}
+
+extern "C" int tcam_conv2d_group(const tcam_conv_prob* probs, int nprob, int B, int fmt,
+                                 int tile, int* oflow, void* stream) {
+    TCAM_REQUIRE(probs && nprob >= 1 && nprob <= kMaxGroup && (fmt == 0 || fmt == 1));
+    TCAM_REQUIRE(tile == -1 || is_group_tile(tile));
+    const Fmt f{(Format)fmt, nullptr, fmt ? oflow : nullptr};
+    ConvX ps[kMaxGroup];
+    bool all_aligned = true, taps = false;
+    for (int i = 0; i < nprob; ++i) {
+        const tcam_conv_prob& q = probs[i];
+        Fmt fi = f;
+        if (fmt) {
+            TCAM_REQUIRE(q.wscale && ((uintptr_t)q.wscale & 15) == 0);
+            fi.wscale = q.wscale;
+        } else {
+            TCAM_REQUIRE(!q.wscale);
+        }
+        const Dst d{q.out, 0, q.out_cstride ? q.out_cstride : q.Cout, q.out_coff};
+        bool aligned;
+        const int rc = build_convx(ps[i], aligned, &q.src, 1, B, q.wt, q.bias, nullptr, &d, 1,
+                                   q.Cout, q.Hout, q.Wout, q.KH, q.KW, q.pad_h, q.pad_w, q.relu,
+                                   nullptr, 0, fi);
+        if (rc != TCAM_OK) return rc;
+        all_aligned = all_aligned && aligned;
+        taps = taps || q.KH * q.KW > 1;
+    }
+    int id = g_force_tile >= 0 && is_group_tile(g_force_tile) ? g_force_tile : tile;
+    if (id < 0)
+        id = !all_aligned ? T_REG_128x64_M16 : taps ? T_DMA_128x128_M16_LW : T_DMA_128x128_M16;
+    if (is_g_tile(id) && !all_aligned) id = T_REG_128x64_M16;
+    // (not with_format: the grouped kernels exist for these two formats only)
+    return fmt ? launch_group_tile<FmtF16>(id, ps, nprob, as_stream(stream))
+               : launch_group_tile<FmtX6>(id, ps, nprob, as_stream(stream));
+}
+
+// ---- host-only queries (no device needed) ----
+extern "C" int tcam_conv_x6_tile_info(int fmt, int id, int* out) {
+    TCAM_REQUIRE(fmt >= 0 && fmt <= 3 && id >= 0 && id < kNumTiles && id != kThinTile && out);
+    const int r = resolve((Format)fmt, id);
+    const TileDesc& d = kTiles[r];
+    const int v[13] = {d.dma, d.bm, d.bn, d.wm, d.wn, d.stages, d.has(M16), d.has(IL),
+                       d.has(LW), d.has(PP), d.has(FP), d.has(GROUP), d.id == id};
+    std::copy(v, v + 13, out);
+    return TCAM_OK;
+}
+
+extern "C" int tcam_conv_x6_plan(const tcam_conv_src* srcs, int nsrc, int B, int Cout, int Hout,
+                                 int Wout, int KH, int KW, int pad_h, int pad_w, int fmt,
+                                 int ndst, int has_residual, int* tile) {
+    TCAM_REQUIRE(tile && fmt >= 0 && fmt <= 3 && ndst >= 1 && ndst <= 3);
+    TCAM_REQUIRE(ndst == 1 || ((fmt == 0 || fmt == 1) && !has_residual && Cout >= 8 * ndst));
+    TCAM_REQUIRE(srcs && (nsrc == 1 || nsrc == 2) && B > 0 && Cout > 0);
+    // build_convx checks the pointers' alignment and reads none of them
+    alignas(16) static char buf[16];
+    Dst d[3];
+    for (int i = 0; i < ndst; ++i) {
+        const int c0 = Cout / 8 * i / ndst * 8;   // near-equal destinations, multiples of 8
+        d[i] = Dst{buf, c0, Cout, c0};
+    }
+    const Fmt f{(Format)fmt, (const float*)buf, nullptr};
+    B = chunk_frames(srcs, nsrc, B, d, ndst, Cout, Hout, Wout, f);   // the first launch's
+    ConvX p;
+    bool aligned;
+    const int rc = build_convx(p, aligned, srcs, nsrc, B, buf, (const float*)buf,
+                               has_residual ? buf : nullptr, d, ndst, Cout, Hout, Wout, KH, KW,
+                               pad_h, pad_w, 0, nullptr, 0, f);
+    if (rc != TCAM_OK) return rc;
+    *tile = plan_tile(p, aligned, srcs, nsrc, ndst, has_residual != 0, f.fmt);
+    return TCAM_OK;
 }

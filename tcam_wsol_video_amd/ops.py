@@ -54,13 +54,27 @@ def _timer_events():
     return e
 
 
-def _timer_arm(lib, e0, e1) -> None:
-    """The next HIP conv call's kernels carry e0 (first dispatch) / e1 (every dispatch)."""
-    check(lib.tcam_timer_arm(e0.cuda_event, e1.cuda_event), "tcam_timer_arm")
+def _timer_begin(lib=None):
+    """None when no launch timer is set, else this launch's (start, end) events: armed on
+    the next HIP conv call of ``lib``, whose kernels carry them (start: the first dispatch,
+    end: every dispatch), or with no ``lib`` (the fp32 conv) the start recorded here."""
+    if _TIMER is None:
+        return None
+    ev = _timer_events()
+    if lib is None:
+        ev[0].record()
+    else:
+        check(lib.tcam_timer_arm(ev[0].cuda_event, ev[1].cuda_event), "tcam_timer_arm")
+    return ev
 
 
-def _timer_disarm(lib) -> None:
-    check(lib.tcam_timer_arm(None, None), "tcam_timer_arm")
+def _timer_end(lib, ev, flops: float, desc: str) -> None:
+    """Close the bracket ``_timer_begin`` opened (same ``lib``) and append the launch."""
+    if lib is None:
+        ev[1].record()
+    else:
+        check(lib.tcam_timer_arm(None, None), "tcam_timer_arm")
+    _TIMER.append(("conv", flops, ev[0], ev[1], desc))
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -126,18 +140,14 @@ def conv2d(srcs: Sequence[ConvSrc], wt: torch.Tensor, bias: torch.Tensor, cout: 
         assert t.dtype == torch.float32 and t.dim() == 4 and t.shape[0] == B
         arr[i] = tcam_conv_src(t.data_ptr(), t.shape[1], t.shape[2], t.shape[3], s.stride,
                                1 if s.up2 else 0)
-    timer = _TIMER
-    if timer is not None:
-        e0, e1 = _timer_events()
-        e0.record()
+    ev = _timer_begin()
     check(lib.tcam_conv2d(arr, len(srcs), B, _ptr(wt), _ptr(bias), _ptr(residual), _ptr(out),
                           cout, hout, wout, ksize, ksize, pad, 1 if relu else 0, _stream()),
           "tcam_conv2d")
-    if timer is not None:
-        e1.record()
+    if ev is not None:
         kdim = wt.shape[0]
-        timer.append(("conv", 2.0 * cout * kdim * B * hout * wout, e0, e1,
-                      f"M{cout} K{kdim} N{B * hout * wout} k{ksize} src{len(srcs)}"))
+        _timer_end(None, ev, 2.0 * cout * kdim * B * hout * wout,
+                   f"M{cout} K{kdim} N{B * hout * wout} k{ksize} src{len(srcs)}")
     return out
 
 
@@ -630,18 +640,14 @@ def stem_f16x3(x: torch.Tensor, st: StemF16) -> torch.Tensor:
     Wo = (W + 2 * st.pad - st.k) // st.stride + 1
     out = s2_empty(B, Ho, Wo, st.cout, x.device)
     tab = st.ktab(x.device)
-    timer = _TIMER
-    if timer is not None:
-        e0, e1 = _timer_events()
-        _timer_arm(lib, e0, e1)
+    ev = _timer_begin(lib)
     check(lib.tcam_stem_f16x3(_ptr(x), _ptr(st.wt), _ptr(st.wscale), _ptr(st.bias), _ptr(tab),
                               st.nk, _ptr(out), B, st.cin, H, W, st.cout, st.k, st.k, st.stride,
                               st.pad, _ptr(f16_overflow_flag(x.device)), _stream()),
           "tcam_stem_f16x3")
-    if timer is not None:
-        _timer_disarm(lib)
-        timer.append(("conv", 2.0 * st.cout * st.cin * st.k * st.k * B * Ho * Wo, e0, e1,
-                      f"M{st.cout} K{st.cin * st.k * st.k} N{B * Ho * Wo} k{st.k}x{st.k} stem"))
+    if ev is not None:
+        _timer_end(lib, ev, 2.0 * st.cout * st.cin * st.k * st.k * B * Ho * Wo,
+                   f"M{st.cout} K{st.cin * st.k * st.k} N{B * Ho * Wo} k{st.k}x{st.k} stem")
     return out
 
 
@@ -799,10 +805,7 @@ def conv2d_x6(srcs: Sequence[ConvSrc], wt: torch.Tensor, bias: torch.Tensor, cou
     if residual is not None:
         assert _lay(residual) == lay
     arr, kdim = _x6_srcs(srcs, B, kh, kw, fmt)
-    timer = _TIMER
-    if timer is not None:
-        e0, e1 = _timer_events()
-        _timer_arm(lib, e0, e1)
+    ev = _timer_begin(lib)
     stream = _stream()
     ws = _x6_workspace(wt.device, stream) if stream_k else None
     if f16:
@@ -824,10 +827,9 @@ def conv2d_x6(srcs: Sequence[ConvSrc], wt: torch.Tensor, bias: torch.Tensor, cou
                                  _ptr(out), cout, hout, wout, kh, kw, ph, pw, 1 if relu else 0,
                                  cstride, out_coff, _ptr(ws), 0 if ws is None else ws.numel(),
                                  stream), "tcam_conv2d_x6")
-    if timer is not None:
-        _timer_disarm(lib)
-        timer.append(("conv", 2.0 * cout * kdim * B * hout * wout, e0, e1,
-                      f"M{cout} K{kdim} N{B * hout * wout} k{kh}x{kw} src{len(srcs)}"))
+    if ev is not None:
+        _timer_end(lib, ev, 2.0 * cout * kdim * B * hout * wout,
+                   f"M{cout} K{kdim} N{B * hout * wout} k{kh}x{kw} src{len(srcs)}")
     return out
 
 
@@ -868,10 +870,7 @@ def bottleneck_f16x3(x: torch.Tensor, c1, c2, c3, ds: bool) -> torch.Tensor:
         raise ValueError("bottleneck_f16x3 takes f16x3 or amp weights")
     _dev(x, c1.wt, c2.wt, c3.wt)
     out = lay_empty(FMT_LAYOUT[fmt], B, H, W, 256, x.device)
-    timer = _TIMER
-    if timer is not None:
-        e0, e1 = _timer_events()
-        _timer_arm(lib, e0, e1)
+    ev = _timer_begin(lib)
     if fmt == "f16x3":
         if any(c.wscale is None for c in (c1, c2, c3)):
             raise ValueError("f16x3 weights need their per-channel scales (wscale)")
@@ -886,11 +885,10 @@ def bottleneck_f16x3(x: torch.Tensor, c1, c2, c3, ds: bool) -> torch.Tensor:
                                       _ptr(c2.wt), _ptr(c2.bias), _ptr(c3.wt), _ptr(c3.bias),
                                       1 if ds else 0, _ptr(out), _stream()),
               "tcam_bottleneck_f16")
-    if timer is not None:
-        _timer_disarm(lib)
+    if ev is not None:
         n = B * H * W
-        flop = 2.0 * n * (64 * cin + 64 * 576 + 256 * (64 + (cin if ds else 0)))
-        timer.append(("conv", flop, e0, e1, f"bottleneck cin{cin} N{n}{' ds' if ds else ''}"))
+        _timer_end(lib, ev, 2.0 * n * (64 * cin + 64 * 576 + 256 * (64 + (cin if ds else 0))),
+                   f"bottleneck cin{cin} N{n}{' ds' if ds else ''}")
     return out
 
 
@@ -926,10 +924,7 @@ def conv2d_x6_multi(srcs: Sequence[ConvSrc], wt: torch.Tensor, bias: torch.Tenso
         dst[i] = tcam_conv_dst(t.data_ptr(), c0, s3_dims(t)[3], coff)
         res.append(t)
         c0 += c
-    timer = _TIMER
-    if timer is not None:
-        e0, e1 = _timer_events()
-        _timer_arm(lib, e0, e1)
+    ev = _timer_begin(lib)
     stream = _stream()
     ws = _x6_workspace(wt.device, stream) if stream_k else None
     if f16:
@@ -943,10 +938,9 @@ def conv2d_x6_multi(srcs: Sequence[ConvSrc], wt: torch.Tensor, bias: torch.Tenso
                                        wout, kh, kw, ph, pw, 1 if relu else 0, dst, len(couts),
                                        _ptr(ws), 0 if ws is None else ws.numel(), stream),
               "tcam_conv2d_x6_multi")
-    if timer is not None:
-        _timer_disarm(lib)
-        timer.append(("conv", 2.0 * cout * kdim * B * hout * wout, e0, e1,
-                      f"M{cout} K{kdim} N{B * hout * wout} k{kh}x{kw} src{len(srcs)} x{len(couts)}"))
+    if ev is not None:
+        _timer_end(lib, ev, 2.0 * cout * kdim * B * hout * wout,
+                   f"M{cout} K{kdim} N{B * hout * wout} k{kh}x{kw} src{len(srcs)} x{len(couts)}")
     return res
 
 
@@ -1004,17 +998,13 @@ def conv2d_group(members: Sequence[ConvMember], tile: int = -1) -> List[torch.Te
         outs.append(out)
         flops += 2.0 * m.cout * kdim * B * m.hout * m.wout
         desc.append(f"M{m.cout} K{kdim} N{B * m.hout * m.wout} k{m.ksize[0]}x{m.ksize[1]}")
-    timer = _TIMER
-    if timer is not None:
-        e0, e1 = _timer_events()
-        _timer_arm(lib, e0, e1)
+    ev = _timer_begin(lib)
     dev = members[0].wt.device
     check(lib.tcam_conv2d_group(arr, len(members), B, 1 if f16 else 0, int(tile),
                                 _ptr(f16_overflow_flag(dev)) if f16 else None, _stream()),
           "tcam_conv2d_group")
-    if timer is not None:
-        _timer_disarm(lib)
-        timer.append(("conv", flops, e0, e1, "group[" + " | ".join(desc) + "]"))
+    if ev is not None:
+        _timer_end(lib, ev, flops, "group[" + " | ".join(desc) + "]")
     return outs
 
 
