@@ -330,6 +330,38 @@ int tcam_std_cam(const float* A, const float* fc_w, const int32_t* cls,
                  float* low, float* cam, uint8_t* cam_u8, int B, int C,
                  int h, int w, int Ho, int Wo, void* stream);
 
+/* The gradient CAM family on a WGAP classifier (cams/gradcam.py: GradCAM, GradCAMpp,
+ * XGradCAM, LayerCAM; cams/core.py:162-193), hooked at the ReLU in front of the pooling:
+ * the gradient of scores[:, c].sum() there is g[k] = fp32(fc_w[c, k] / (h w)) at every
+ * position, so no backward pass runs.  Per frame b, with c = cls[b]:
+ *   w_k    = g_k | h w g_k^2 relu(g_k) | sum_p(g_k A_k[p]) / sum_p A_k[p] | relu(g_k)
+ *            (XGradCAM's ratio as (g_k S_k) / S_k, S_k = sum_p A_k[p]: NaN, and the channel
+ *            dropped, where S_k is 0, NaN or infinite)
+ *   low[b] = minmax_normalise( relu( nansum_k w_k A[b, k] ) )            (h, w)
+ *   cam[b] = bilinear(align_corners=False)(low[b]) to (Ho, Wo); cam_u8 optional,
+ * the normalisation, NaN handling, resize and quantisation being tcam_std_cam's.
+ * fc_w: the true (classes, C) weight.  exps: NULL, or (C,) int32 e_k where A is stored
+ * times 2^e_k (the f16x3 features): w_k is then multiplied by 2^-e_k (exact).
+ * ws: tcam_grad_cam_ws_bytes(B, C, h w) bytes.  Deterministic (no atomics).  h w <= 4096.
+ * The _s3 / _s2 / _s1 forms take A (B, h, w, C/8 groups) in that layout (C % 8 == 0). */
+#define TCAM_GRAD_GRADCAM 0
+#define TCAM_GRAD_GRADCAMPP 1
+#define TCAM_GRAD_XGRADCAM 2
+#define TCAM_GRAD_LAYERCAM 3
+size_t tcam_grad_cam_ws_bytes(int B, int C, int hw);
+int tcam_grad_cam(const float* A, const float* fc_w, const int32_t* cls, const int32_t* exps,
+                  int method, float* ws, float* low, float* cam, uint8_t* cam_u8, int B, int C,
+                  int h, int w, int Ho, int Wo, void* stream);
+int tcam_grad_cam_s3(const void* A, const float* fc_w, const int32_t* cls, const int32_t* exps,
+                     int method, float* ws, float* low, float* cam, uint8_t* cam_u8, int B,
+                     int C, int h, int w, int Ho, int Wo, void* stream);
+int tcam_grad_cam_s2(const void* A, const float* fc_w, const int32_t* cls, const int32_t* exps,
+                     int method, float* ws, float* low, float* cam, uint8_t* cam_u8, int B,
+                     int C, int h, int w, int Ho, int Wo, void* stream);
+int tcam_grad_cam_s1(const void* A, const float* fc_w, const int32_t* cls, const int32_t* exps,
+                     int method, float* ws, float* low, float* cam, uint8_t* cam_u8, int B,
+                     int C, int h, int w, int Ho, int Wo, void* stream);
+
 /* Temporal CAM aggregation (datasets/wsol_loader.py:591-601, 630-635):
  * out[i] = max_j renorm(cams[idx[i, j]]) over the (k+1) frames j with
  * idx >= 0, renorm(c) = nan_to_num(exp(t (c + 1e-6)) / max) when t > 0,

@@ -106,6 +106,11 @@ SIGNATURES = {
     "tcam_wgap": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "tcam_seghead_cam": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "tcam_std_cam": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "tcam_grad_cam_ws_bytes": (C.c_size_t, [_I, _I, _I]),
+    "tcam_grad_cam": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "tcam_grad_cam_s3": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "tcam_grad_cam_s2": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "tcam_grad_cam_s1": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "tcam_temporal_max": (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
     "tcam_temporal_cam": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _F, _P, _P]),
     "tcam_topk_flags": (_I, [_P, _P, _P, _P, _I, _I, _P]),

@@ -21,7 +21,7 @@ def _needs(obj: str, src: str) -> bool:
         return True
     t = os.path.getmtime(obj)
     deps = [src, os.path.join(CSRC, "common.h"), os.path.join(CSRC, "s3_util.h"),
-            os.path.join(CSRC, "vgg_train_addr.h"),
+            os.path.join(CSRC, "vgg_train_addr.h"), os.path.join(CSRC, "grad_cam.h"),
             os.path.join(os.path.dirname(HERE), "include", "tcam_hip.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 

@@ -3,6 +3,7 @@
 // layer4 activations + min-max normalise + bilinear resize), the temporal
 // max over neighbour-frame CAMs, and the top-1/top-5 rank of the target.
 #include "common.h"
+#include "grad_cam.h"
 
 namespace {
 
@@ -74,7 +75,10 @@ __global__ void seghead_cam_kernel(const float* __restrict__ x, const float* __r
 //                                              one NaN pixel makes both NaN, the map 0)
 //   nan_to_num                                (inference_wsol.py:323)
 //   cam = bilinear(low -> Ho x Wo, align_corners=False) (inference_wsol.py:342-346)
+// GRAD: the gradient family's map (tcam_grad_cam): the frame's own weight row fcw[b] (the
+// channel weights of grad_weights_kernel) and relu(nansum) (gradcam.py:48, core.py:186-187).
 constexpr int STD_MAX_HW = 4096;
+template <bool GRAD>
 __global__ __launch_bounds__(1024) void std_cam_kernel(
     const float* __restrict__ A, const float* __restrict__ fcw, const int32_t* __restrict__ cls,
     float* __restrict__ low_out, float* __restrict__ cam, uint8_t* __restrict__ cam_u8, int C,
@@ -84,14 +88,14 @@ __global__ __launch_bounds__(1024) void std_cam_kernel(
     const int b = blockIdx.x;
     const int hw = h * w;
     const float* Ab = A + (long)b * C * hw;
-    const float* wr = fcw + (long)cls[b] * C;
+    const float* wr = fcw + (long)(GRAD ? b : cls[b]) * C;
     for (int p = threadIdx.x; p < hw; p += blockDim.x) {
         float s = 0.f;
         for (int c = 0; c < C; ++c) {
             float v = wr[c] * Ab[(long)c * hw + p];
             if (v == v) s += v;  // nansum
         }
-        low[p] = s;
+        low[p] = GRAD ? relu_nan(s) : s;
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -147,6 +151,22 @@ __global__ __launch_bounds__(1024) void std_cam_kernel(
         if (cam) cam[(long)b * Ho * Wo + p] = v;
         if (cam_u8) cam_u8[(long)b * Ho * Wo + p] = (uint8_t)(int)((double)v * 255.0);
     }
+}
+
+// XGradCAM's sum of A over the positions of a plain NCHW plane, a wave per (frame, channel):
+// lanes stride the plane, then a butterfly adds the 64 partial sums in a fixed order.
+__global__ __launch_bounds__(256) void xgrad_sums_kernel(const float* __restrict__ A,
+                                                         float* __restrict__ part, int C,
+                                                         int hw) {
+    const int b = blockIdx.y;
+    const int k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (k >= C) return;
+    const int lane = threadIdx.x & 63;
+    const float* src = A + ((long)b * C + k) * hw;
+    float s = 0.f;
+    for (int p = lane; p < hw; p += 64) s += src[p];
+    s = wave_sum(s);
+    if (lane == 0) part[(long)b * C + k] = s;
 }
 
 // Temporal max over neighbour-frame CAMs, one workgroup per output.
@@ -324,8 +344,36 @@ extern "C" int tcam_std_cam(const float* A, const float* fc_w, const int32_t* cl
                             int Wo, void* stream) {
     TCAM_REQUIRE(A && fc_w && cls && B > 0 && C > 0 && h > 0 && w > 0 && h * w <= STD_MAX_HW);
     TCAM_REQUIRE(Ho > 0 && Wo > 0);
-    std_cam_kernel<<<B, 1024, 0, as_stream(stream)>>>(A, fc_w, cls, low, cam, cam_u8, C, h, w,
-                                                      Ho, Wo);
+    std_cam_kernel<false><<<B, 1024, 0, as_stream(stream)>>>(A, fc_w, cls, low, cam, cam_u8, C,
+                                                             h, w, Ho, Wo);
+    TCAM_CHECK_LAUNCH();
+    return TCAM_OK;
+}
+
+extern "C" size_t tcam_grad_cam_ws_bytes(int B, int C, int hw) {
+    if (B <= 0 || C <= 0 || hw <= 0) return 0;
+    const size_t nchunks = (size_t)(hw + GRAD_CHUNK - 1) / GRAD_CHUNK;
+    return (size_t)B * C * (1 + nchunks) * sizeof(float);
+}
+
+extern "C" int tcam_grad_cam(const float* A, const float* fc_w, const int32_t* cls,
+                             const int32_t* exps, int method, float* ws, float* low, float* cam,
+                             uint8_t* cam_u8, int B, int C, int h, int w, int Ho, int Wo,
+                             void* stream) {
+    TCAM_REQUIRE(A && fc_w && cls && ws && B > 0 && C > 0 && h > 0 && w > 0 &&
+                 h * w <= STD_MAX_HW);
+    TCAM_REQUIRE(Ho > 0 && Wo > 0 && grad_method_ok(method));
+    hipStream_t st = as_stream(stream);
+    float* part = ws + (long)B * C;
+    if (method == TCAM_GRAD_XGRADCAM) {
+        xgrad_sums_kernel<<<dim3(cdiv(C, 4), B), 256, 0, st>>>(A, part, C, h * w);
+        TCAM_CHECK_LAUNCH();
+    }
+    const long total = (long)B * C;
+    grad_weights_kernel<<<cdiv(total, 256), 256, 0, st>>>(fc_w, cls, exps, part, ws, C, h * w, 1,
+                                                          method, total);
+    TCAM_CHECK_LAUNCH();
+    std_cam_kernel<true><<<B, 1024, 0, st>>>(A, ws, nullptr, low, cam, cam_u8, C, h, w, Ho, Wo);
     TCAM_CHECK_LAUNCH();
     return TCAM_OK;
 }

@@ -13,6 +13,7 @@
 // All are HBM-bound: one pass over their input, 6 B per element.
 #include "common.h"
 #include "s3_util.h"
+#include "grad_cam.h"
 
 namespace {
 
@@ -409,8 +410,10 @@ __global__ void resize_ac_bwd_kernel(const float* __restrict__ dout, float* __re
 //   low = nansum_c w[cls, c] * A[c]; min-max normalise (a NaN pixel makes min and max
 //   NaN, as low.min() / low.max() do: the whole map becomes 0); nan_to_num;
 //   bilinear(align_corners=False) to (Ho, Wo).
+// GRAD: the gradient family's map (tcam_grad_cam_*): the frame's own weight row fcw[b] and
+// relu(nansum), as std_cam_kernel<true> of cam.hip.
 constexpr int STD_MAX_HW = 4096;
-template <class L>
+template <class L, bool GRAD>
 __global__ __launch_bounds__(1024) void std_cam_s3_kernel(
     const uint8_t* __restrict__ A, const float* __restrict__ fcw, const int32_t* __restrict__ cls,
     float* __restrict__ low_out, float* __restrict__ cam, uint8_t* __restrict__ cam_u8, int G,
@@ -420,7 +423,7 @@ __global__ __launch_bounds__(1024) void std_cam_s3_kernel(
     const int b = blockIdx.x;
     const int hw = h * w;
     const int C = 8 * G;
-    const float* wr = fcw + (long)cls[b] * C;
+    const float* wr = fcw + (long)(GRAD ? b : cls[b]) * C;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
     for (int p = wid; p < hw; p += nw) {
         const uint8_t* src = A + ((long)b * hw + p) * G * L::GB;
@@ -434,7 +437,7 @@ __global__ __launch_bounds__(1024) void std_cam_s3_kernel(
             }
         }
         s = wave_sum(s);
-        if (lane == 0) low[p] = s;
+        if (lane == 0) low[p] = GRAD ? relu_nan(s) : s;
     }
     __syncthreads();
     float mn = INFINITY;
@@ -487,6 +490,31 @@ __global__ __launch_bounds__(1024) void std_cam_s3_kernel(
                          ly1 * (lx0 * low[y1 * w + x0] + lx1 * low[y1 * w + x1]);
         if (cam) cam[(long)b * Ho * Wo + p] = v;
         if (cam_u8) cam_u8[(long)b * Ho * Wo + p] = (uint8_t)(int)((double)v * 255.0);
+    }
+}
+
+// XGradCAM's sums of A over a chunk of GRAD_CHUNK positions: grid (chunks, B), a thread per
+// 8-channel group (strided where G > blockDim) adds its chunk's pixels in order, as
+// pool_partial_kernel; grad_weights_kernel adds the chunks.  The one pass of the family
+// that reduces over positions, spread over chunks x frames workgroups.
+template <class L>
+__global__ __launch_bounds__(1024) void xgrad_partial_kernel(const uint8_t* __restrict__ x,
+                                                             float* __restrict__ part, int G,
+                                                             int HW, int nchunks) {
+    const int b = blockIdx.y, ch = blockIdx.x;
+    const int p0 = ch * GRAD_CHUNK, p1 = min(HW, p0 + GRAD_CHUNK);
+    float* dst = part + ((long)b * nchunks + ch) * 8 * G;
+    for (int g = threadIdx.x; g < G; g += blockDim.x) {
+        float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        const uint8_t* src = x + (((long)b * HW + p0) * G + g) * L::GB;
+#pragma unroll 8
+        for (int p = p0; p < p1; ++p, src += (long)G * L::GB) {
+            const G8 v = L::load(src);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s[e] += v.v[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dst[8 * g + e] = s[e];
     }
 }
 
@@ -626,8 +654,36 @@ static int std_cam(const void* A, const float* fc_w, const int32_t* cls, float* 
                    uint8_t* cam_u8, int B, int C, int h, int w, int Ho, int Wo, void* stream) {
     TCAM_REQUIRE(A && fc_w && cls && B > 0 && C > 0 && C % 8 == 0 && h > 0 && w > 0 &&
                  h * w <= STD_MAX_HW && Ho > 0 && Wo > 0);
-    std_cam_s3_kernel<L><<<B, 1024, 0, as_stream(stream)>>>((const uint8_t*)A, fc_w, cls, low, cam,
-                                                         cam_u8, C / 8, h, w, Ho, Wo);
+    std_cam_s3_kernel<L, false><<<B, 1024, 0, as_stream(stream)>>>(
+        (const uint8_t*)A, fc_w, cls, low, cam, cam_u8, C / 8, h, w, Ho, Wo);
+    TCAM_CHECK_LAUNCH();
+    return TCAM_OK;
+}
+
+// The gradient CAM family on S3 / S2 / S1 features (grad_cam.h): the channel weights into
+// ws, then std_cam's kernel with the frame's own weight row and a ReLU.
+template <class L>
+static int grad_cam(const void* A, const float* fc_w, const int32_t* cls, const int32_t* exps,
+                    int method, float* ws, float* low, float* cam, uint8_t* cam_u8, int B, int C,
+                    int h, int w, int Ho, int Wo, void* stream) {
+    TCAM_REQUIRE(A && fc_w && cls && ws && B > 0 && C > 0 && C % 8 == 0 && h > 0 && w > 0 &&
+                 h * w <= STD_MAX_HW && Ho > 0 && Wo > 0 && grad_method_ok(method));
+    hipStream_t st = as_stream(stream);
+    const int G = C / 8, HW = h * w;
+    const int nchunks = (HW + GRAD_CHUNK - 1) / GRAD_CHUNK;
+    float* part = ws + (long)B * C;
+    if (method == TCAM_GRAD_XGRADCAM) {
+        const int threads = std::min(1024, (G + 63) / 64 * 64);
+        xgrad_partial_kernel<L><<<dim3(nchunks, B), threads, 0, st>>>((const uint8_t*)A, part, G,
+                                                                      HW, nchunks);
+        TCAM_CHECK_LAUNCH();
+    }
+    const long total = (long)B * C;
+    grad_weights_kernel<<<cdiv(total, 256), 256, 0, st>>>(fc_w, cls, exps, part, ws, C, HW,
+                                                          nchunks, method, total);
+    TCAM_CHECK_LAUNCH();
+    std_cam_s3_kernel<L, true><<<B, 1024, 0, st>>>((const uint8_t*)A, ws, nullptr, low, cam,
+                                                   cam_u8, G, h, w, Ho, Wo);
     TCAM_CHECK_LAUNCH();
     return TCAM_OK;
 }
@@ -698,6 +754,13 @@ extern "C" int tcam_s3_to_s2(const void* in, void* out, long groups, void* strea
                                       float* low, float* cam, uint8_t* cam_u8, int B, int C,   \
                                       int h, int w, int Ho, int Wo, void* stream) {            \
         return std_cam<L>(A, fc_w, cls, low, cam, cam_u8, B, C, h, w, Ho, Wo, stream);         \
+    }                                                                                          \
+    extern "C" int tcam_grad_cam_##SUF(const void* A, const float* fc_w, const int32_t* cls,    \
+                                       const int32_t* exps, int method, float* ws, float* low, \
+                                       float* cam, uint8_t* cam_u8, int B, int C, int h,       \
+                                       int w, int Ho, int Wo, void* stream) {                  \
+        return grad_cam<L>(A, fc_w, cls, exps, method, ws, low, cam, cam_u8, B, C, h, w, Ho,   \
+                           Wo, stream);                                                        \
     }
 
 TCAM_LAYOUT_ENTRIES(s3, LayS3)

@@ -95,6 +95,94 @@ class CAM:
         return out[0] if out.shape[0] == 1 else out
 
 
+class _GradCAM:
+    """The gradient CAM family on the WGAP classifier (cams/gradcam.py:27-81), batched with
+    one class per frame.  The hook is the ReLU in front of AdaptiveAvgPool2d(1) + Linear, so
+    the gradient of ``scores[:, c].sum()`` there is ``fc.weight[c] / (h w)`` at every
+    position: the channel weights come from the classifier weight in closed form
+    (csrc/grad_cam.h) and no backward pass runs; ``scores`` is accepted and not read."""
+
+    method: str = ""
+
+    def __init__(self, model: STDClassifier, target_layer: str = "encoder.layer4.2.relu3"):
+        from .models import TRG_LAYERS
+        if target_layer not in TRG_LAYERS.values():
+            raise NotImplementedError(f"{type(self).__name__} hook {target_layer!r}: the "
+                                      f"encoders' last stages are {sorted(TRG_LAYERS.values())}")
+        self.model = model
+        self.target_layer = target_layer
+
+    def __call__(self, class_idx, scores=None, normalized: bool = True, reshape=None):
+        A = self.model.features
+        if A is None:
+            raise AssertionError("Inputs need to be forwarded in the model for the conv "
+                                 "features to be hooked")
+        if not normalized:
+            raise NotImplementedError
+        n = ops.s3_dims(A)[0] if ops.is_act(A) else A.shape[0]
+        cls = torch.as_tensor(class_idx, dtype=torch.int32).reshape(-1)
+        if cls.numel() == 1 and n > 1:
+            cls = cls.expand(n).contiguous()
+        size = reshape if reshape is not None else (
+            A.shape[1:3] if ops.is_act(A) else A.shape[2:])
+        w = self.model.classification_head.fc.weight.detach().contiguous()
+        low, cam, _ = ops.grad_cam(A, w, cls, tuple(size), self.method,
+                                   exps=self.model.features_exp, want_u8=False)
+        out = cam if reshape is not None else low
+        return out[0] if out.shape[0] == 1 else out
+
+
+class GradCAM(_GradCAM):
+    """gradcam.py:84-129: w_k = mean_p g."""
+    method = "GradCam"
+
+
+class GradCAMpp(_GradCAM):
+    """gradcam.py:132-198: w_k = sum_p g^2 relu(g) (the alpha division acts on a copy)."""
+    method = "GradCAMpp"
+
+
+class XGradCAM(_GradCAM):
+    """gradcam.py:343-394: w_k = sum_p (g A_k) / sum_p A_k."""
+    method = "XGradCAM"
+
+
+class LayerCAM(_GradCAM):
+    """gradcam.py:397-443: w_k[p] = relu(g)."""
+    method = "LayerCAM"
+
+
+# dlib/configure/constants.py:59-89: the STD_CL methods built here, and the ones that are not
+STD_CAM_METHODS = {"CAM": CAM, "GradCam": GradCAM, "GradCAMpp": GradCAMpp,
+                   "XGradCAM": XGradCAM, "LayerCAM": LayerCAM}
+STD_CAM_METHODS_NOT_BUILT = ("SmoothGradCAMpp", "ScoreCAM", "SSCAM", "ISCAM", "WILDCAT", "GAP",
+                             "MaxPOL", "LogSumExp")
+
+
+def check_std_cam_method(method: str) -> str:
+    """The STD_CL ``--method`` names: the five built ones pass, the reference's other
+    methods are refused as not built, anything else as unknown."""
+    if method in STD_CAM_METHODS:
+        return method
+    if method in STD_CAM_METHODS_NOT_BUILT:
+        raise ValueError(f"--method {method}: not built (the STD_CL methods of this build are "
+                         f"{', '.join(STD_CAM_METHODS)})")
+    raise ValueError(f"--method {method}: unknown method (the STD_CL methods of this build are "
+                     f"{', '.join(STD_CAM_METHODS)})")
+
+
+def build_std_cam_extractor(model, args):
+    """cams/__init__.py:53-117 for the WGAP classifier: the extractor of ``args.method`` on
+    TRG_LAYERS[encoder] (and FC_LAYERS[encoder] for CAM)."""
+    from .models import FC_LAYERS, TRG_LAYERS
+    model.eval()
+    method = check_std_cam_method(args.method)
+    enc = args.model["encoder_name"] if hasattr(args, "model") else args.encoder_name
+    if method == "CAM":
+        return CAM(model, target_layer=TRG_LAYERS[enc], fc_layer=FC_LAYERS[enc])
+    return STD_CAM_METHODS[method](model, target_layer=TRG_LAYERS[enc])
+
+
 class CAMComputer:
     """Batched evaluation of one split (inference_wsol.py:105-457).
 
@@ -109,7 +197,7 @@ class CAMComputer:
     def __init__(self, model, cam_curve_interval: float = .001,
                  iou_threshold_list: Sequence[int] = (30, 50, 70), device="cuda",
                  overlap: bool = True, keep_fcams: bool = False, fwd_streams: int = 1,
-                 temporal=None, multi_contour_eval: bool = False):
+                 temporal=None, multi_contour_eval: bool = False, method: str = "CAM"):
         """fwd_streams > 1 pipelines consecutive clips: clip k+1's forward may run while
         clip k's is still in flight (their small layers fill each other's idle CUs); the
         CAMs a call returns are then complete only after :meth:`synchronize`.
@@ -121,8 +209,12 @@ class CAMComputer:
         (BASELINE configs[4]).
 
         ``multi_contour_eval`` (``--box_v2_metric True``, parseit.py:684-689): every
-        contour's box counts, a tau scores its best IoU (wsol_metrics.py:170-181, 342-368)."""
+        contour's box counts, a tau scores its best IoU (wsol_metrics.py:170-181, 342-368).
+
+        ``method`` (STD_CL models only): the stage-1 CAM method, ``"CAM"`` or one of the
+        gradient family (``GradCam``, ``GradCAMpp``, ``XGradCAM``, ``LayerCAM``)."""
         self.model = model.eval()
+        self.method = check_std_cam_method(method)
         self.temporal = temporal
         self.keep_fcams = keep_fcams   # also materialise model.cams (fcams) per clip
         self.device = torch.device(device)
@@ -257,8 +349,14 @@ class CAMComputer:
                 cam, cam_u8 = m.cam, m.cam_u8
             elif isinstance(m, STDClassifier):
                 logits = m(images)
-                _, cam, cam_u8 = ops.std_cam(m.features, features_fc_weight(m), targets,
-                                             tuple(images.shape[2:]))
+                if self.method == "CAM":
+                    _, cam, cam_u8 = ops.std_cam(m.features, features_fc_weight(m), targets,
+                                                 tuple(images.shape[2:]))
+                else:
+                    fw = m.classification_head.fc.weight.detach().contiguous()
+                    _, cam, cam_u8 = ops.grad_cam(m.features, fw, targets,
+                                                  tuple(images.shape[2:]), self.method,
+                                                  exps=m.features_exp)
             else:
                 raise TypeError(type(m))
         finally:

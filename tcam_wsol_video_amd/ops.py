@@ -219,6 +219,43 @@ def std_cam(A: torch.Tensor, fc_w: torch.Tensor, cls: torch.Tensor, size: Tuple[
     return low, cam, u8
 
 
+# dlib/configure/constants.py's method names -> tcam_grad_cam's method ids (TCAM_GRAD_*)
+GRAD_CAM_METHODS = {"GradCam": 0, "GradCAMpp": 1, "XGradCAM": 2, "LayerCAM": 3}
+
+
+def grad_cam(A: torch.Tensor, fc_w: torch.Tensor, cls: torch.Tensor, size: Tuple[int, int],
+             method: str, exps: Optional[torch.Tensor] = None, want_u8: bool = True):
+    """GradCAM / GradCAM++ / XGradCAM / LayerCAM of the layer hooked in front of WGAP:
+    (low-res normalised, resized, uint8), as :func:`std_cam`.  ``fc_w`` is the true
+    (classes, C) weight; ``exps`` the per-channel exponents of f16x3 features
+    (``model.features_exp``) or None."""
+    lib = _lib.load()
+    if method not in GRAD_CAM_METHODS:
+        raise ValueError(f"grad_cam method {method!r}: one of {sorted(GRAD_CAM_METHODS)}")
+    cls = cls.to(device=A.device, dtype=torch.int32).contiguous()
+    if exps is not None:
+        exps = exps.to(device=A.device, dtype=torch.int32).contiguous()
+    _dev(A, fc_w, cls, exps)
+    if is_act(A):
+        B, h, w, Cc = s3_dims(A)
+        name = f"tcam_grad_cam_{_lay(A)}"
+    else:
+        B, Cc, h, w = A.shape
+        name = "tcam_grad_cam"
+    if fc_w.dtype != torch.float32 or fc_w.dim() != 2 or fc_w.shape[1] != Cc:
+        raise ValueError(f"fc_w must be (classes, {Cc}) float32, got {tuple(fc_w.shape)}")
+    if exps is not None and exps.numel() != Cc:
+        raise ValueError(f"exps must hold {Cc} exponents, got {exps.numel()}")
+    ws = torch.empty(int(lib.tcam_grad_cam_ws_bytes(B, Cc, h * w)) // 4, device=A.device)
+    low = torch.empty((B, h, w), device=A.device)
+    cam = torch.empty((B, size[0], size[1]), device=A.device)
+    u8 = torch.empty((B, size[0], size[1]), device=A.device, dtype=torch.uint8) if want_u8 else None
+    check(getattr(lib, name)(_ptr(A), _ptr(fc_w), _ptr(cls), _ptr(exps),
+                             GRAD_CAM_METHODS[method], _ptr(ws), _ptr(low), _ptr(cam), _ptr(u8),
+                             B, Cc, h, w, size[0], size[1], _stream()), name)
+    return low, cam, u8
+
+
 def temporal_max(cams: torch.Tensor, idx: torch.Tensor, t: float = 0.0) -> torch.Tensor:
     """out[i] = max_j renorm(cams[idx[i, j]]) (idx < 0 = absent)."""
     lib = _lib.load()

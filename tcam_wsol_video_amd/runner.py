@@ -55,16 +55,42 @@ def _bool(s: str) -> bool:
     raise argparse.ArgumentTypeError(s)
 
 
+def check_method(args) -> None:
+    """--task STD_CL: ``--method`` is one of the stage-1 methods built here
+    (inference.STD_CAM_METHODS); the reference's other methods are refused as not built and
+    anything else as unknown, by name.  --task TCAM never reads it (SegmentationCam)."""
+    if args.task != STD_CL:
+        return
+    from .inference import check_std_cam_method
+    try:
+        check_std_cam_method(args.method)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if getattr(args, "std_cams_roi_file", None) and not args.store_std_cams:
+        raise SystemExit("--std_cams_roi_file needs --store_std_cams")
+
+
+class _Parser(argparse.ArgumentParser):
+    """parse_args also runs the checks that span several flags (parseit.py's asserts)."""
+
+    def parse_args(self, *a, **kw):
+        args = super().parse_args(*a, **kw)
+        check_method(args)
+        return args
+
+
 def parser(train: bool) -> argparse.ArgumentParser:
     """The TCAM subset of parseit.get_args (parseit.py:82-579), same flag names."""
-    ap = argparse.ArgumentParser(description="TCAM " + ("training" if train else "evaluation"))
+    ap = _Parser(description="TCAM " + ("training" if train else "evaluation"))
     a = ap.add_argument
     a("--task", default=TCAM, choices=(TCAM, STD_CL))
     a("--dataset", default=YTOV22,
       help="dataset name (constants.py:189-194); CUB / ILSVRC / YTO validate at 250 tau")
     a("--encoder_name", default="resnet50", choices=("resnet50", "vgg16", "inceptionv3"))
     a("--arch", default=None)
-    a("--method", default="CAM")
+    a("--method", default="CAM",
+      help="--task STD_CL: the stage-1 CAM method (constants.py:33-42): CAM, GradCam, "
+           "GradCAMpp, XGradCAM or LayerCAM")
     a("--spatial_pooling", default="WGAP", choices=("WGAP",))
     a("--num_classes", type=int, default=10)
     a("--batch_size", type=int, default=32)
@@ -168,6 +194,13 @@ def parser(train: bool) -> argparse.ArgumentParser:
     else:
         a("--checkpoint", default=None, help="folder holding <step>_best_model.pth")
         a("--splits", default="test")
+        a("--store_std_cams", default=None,
+          help="--task STD_CL: instead of evaluating, store every frame's low-resolution "
+               "--method CAM of its label as <id>.pt in this folder (the --std_cams_folder "
+               "of main.py --task TCAM; inference_wsol.py:1072-1129)")
+        a("--std_cams_roi_file", default=None,
+          help="with --store_std_cams: also write the id,thresh ROI file (the trainer's "
+               "--std_cams_thresh_file)")
     return ap
 
 
@@ -369,7 +402,8 @@ def evaluate(model, split: Split, args, dev, collect: Optional[dict] = None,
     # box_v2_metric -> multi_contour_eval = multi_iou_eval = True (parseit.py:684-689)
     comp = CAMComputer(model, cam_curve_interval=cam_curve_interval, device=dev,
                        fwd_streams=args.fwd_streams if temporal is None else 1,
-                       temporal=temporal, multi_contour_eval=bool(args.box_v2_metric))
+                       temporal=temporal, multi_contour_eval=bool(args.box_v2_metric),
+                       method=args.method if args.task == STD_CL else "CAM")
     if temporal is None:
         order = distributed_sampler_indices(len(split), rank, world)
         batches = [order[k:k + args.batch_size] for k in range(0, len(order), args.batch_size)]
@@ -461,6 +495,72 @@ def _splits(args, names: Sequence[str]) -> Dict[str, Split]:
     return out
 
 
+def store_std_cams(model, split: Split, args, dev, fdout: str,
+                   roi_file: Optional[str] = None) -> int:
+    """Store the low-resolution ``args.method`` CAM of every frame of ``split`` — the frames
+    of a shot-indexed split included — with its label as the class
+    (inference_wsol.py:1072-1129): this rank's strided shard of ``split.ids`` in batches of
+    ``args.batch_size``, one batched forward and one extractor call per batch.  Returns the
+    number of frames this rank stored."""
+    from .camstore import build_store_std_cam_low
+    from .inference import build_std_cam_extractor
+    rank, world = rank_world()
+    extractor = build_std_cam_extractor(model, args)
+    tf = FR.get_eval_tranforms(args.crop_size)
+    mine = split.ids[rank::world]
+
+    def batches():
+        for k in range(0, len(mine), args.batch_size):
+            ids = mine[k:k + args.batch_size]
+            x, _ = device_frames(split, ids, dev, tf)
+            yield x, torch.tensor([split.labels[i] for i in ids], device=dev), ids
+
+    def extract(images, targets):
+        model(images)
+        cams = extractor(targets, None, normalized=True, reshape=None)
+        return cams[None] if cams.ndim == 2 else cams
+
+    return build_store_std_cam_low(extract, batches(), fdout, roi_file)
+
+
+def _store_main(model, args, dev) -> int:
+    """eval.py --task STD_CL --store_std_cams DIR [--std_cams_roi_file FILE]: every split of
+    --splits goes into DIR; each (split, rank) writes its own part of the ROI file, which
+    rank 0 joins in (split, rank) order."""
+    if args.task != STD_CL:
+        raise SystemExit("--store_std_cams stores the stage-1 CAMs: it needs --task STD_CL")
+    rank, world = rank_world()
+    counts, parts = {}, []
+    for name, split in _splits(args, args.splits.split(",")).items():
+        part = None
+        if args.std_cams_roi_file:
+            names = [f"{args.std_cams_roi_file}.{name}.{r}" for r in range(world)]
+            parts += names
+            part = names[rank]
+        n = torch.tensor([store_std_cams(model, split, args, dev, args.store_std_cams, part)],
+                         device=dev)
+        if dist.is_initialized():
+            dist.all_reduce(n)
+        counts[name] = int(n.item())
+    if dist.is_initialized():
+        dist.barrier()
+    if rank == 0:
+        if args.std_cams_roi_file:
+            with open(args.std_cams_roi_file, "w") as out:
+                for p in parts:
+                    with open(p) as f:
+                        out.write(f.read())
+                    os.remove(p)
+        print(json.dumps({"task": args.task, "encoder": args.encoder_name,
+                          "method": args.method, "store_std_cams": args.store_std_cams,
+                          "std_cams_roi_file": args.std_cams_roi_file, "world": world,
+                          "frames": sum(counts.values()), "frames_per_split": counts}),
+              flush=True)
+    if dist.is_initialized():
+        dist.destroy_process_group()
+    return 0
+
+
 def eval_main(argv=None, collect: Optional[dict] = None) -> int:
     args = parser(train=False).parse_args(argv)
     dev = _init_dist(args)
@@ -474,6 +574,8 @@ def eval_main(argv=None, collect: Optional[dict] = None) -> int:
     model = model.to(dev).eval()
     if args.amp_eval:   # inference_wsol.py:258-302: autocast(enabled=amp_eval)
         model.conv_precision = "amp"
+    if args.store_std_cams:
+        return _store_main(model, args, dev)
     res = {}
     for name, split in _splits(args, args.splits.split(",")).items():
         res[name] = evaluate(model, split, args, dev, collect)
