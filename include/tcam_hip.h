@@ -398,7 +398,10 @@ void tcam_bbox_set_chunks(int n);
  * findContours(u8 > L, RETR_TREE, CHAIN_APPROX_SIMPLE), as
  * (x0, y0, min(x0+w, W-1), min(y0+h, H-1)); [0,0,0,0] if none.
  *   cam_u8: (B, H, W);  boxes: (B, 256, 4) int32 (row L; rows >= max unused);
- *   vmax: (B,) int32 = max(cam_u8).  ws: tcam_bbox_ws_bytes(B, H, W) bytes.
+ *   vmax: (B,) int32 = max(cam_u8).  ws: tcam_bbox_ws_bytes(B, H, W) bytes, 256-byte
+ *   aligned: psi, the level tables, the sorted sweep's hooked-root lists (4 level ranges per
+ *   frame at the most), the psi-sorted pixel list and its level offsets — 354312 bytes per
+ *   224 x 224 frame, plus under 1 KB of alignment per call.
  */
 size_t tcam_bbox_ws_bytes(int B, int H, int W);
 int tcam_bbox_levels(const uint8_t* cam_u8, int32_t* boxes, int32_t* vmax,
@@ -408,9 +411,10 @@ int tcam_bbox_levels(const uint8_t* cam_u8, int32_t* boxes, int32_t* vmax,
  * 2 * B * 16 * 16 uint64 receiving per-phase s_memrealtime ticks of the bbox
  * kernels, or NULL to disable. */
 int tcam_bbox_set_debug(uint64_t* buf);
-/* Fill-stage implementation: 0 = wave-parallel clamp scans per line (default), 1 = LDS
- * sweeps (round 1), 2 = register-line sweeps (round 2), kept for A/B timing.  All give
- * identical psi. */
+/* Fill-stage implementation for frames up to 256 x 256: 0 = wave-parallel clamp scans per
+ * line (default), 1 = LDS sweeps (fill_kernel), the independent cross-check.  Identical psi.
+ * (Debug: 100 + n = n waves sweep the lines of the clamp-scan fill; 1000 + k = at most k row +
+ * column passes, 1000 = no limit.)  Any other value returns TCAM_E_ARG and changes nothing. */
 int tcam_bbox_fill_variant(int v);
 /* Re-layout of `groups` 8-channel groups between the S2 (f16x3) and S3 (x6) activation
  * layouts: S2 -> S3 exact; S3 -> S2 rounds to the 22-bit pair (|x| <= 65504). */
@@ -422,11 +426,12 @@ int tcam_bbox_scan_line(const uint8_t* p, const uint8_t* u, uint8_t* out, int n,
                         void* stream);
 /* Level-stage implementation where a level sweep applies (frames up to 224 x 224):
  * 0 = sorted-list sweep (default: new pixels from the fill's psi-sorted pixel list, per-root
- * boxes), 1 = per-level CCL (level_kernel) always, 2 = incremental sweep (round 2).
- * Identical boxes. */
+ * boxes), 1 = per-level CCL (level_kernel) always, the independent cross-check.  Identical
+ * boxes.  Any other value returns TCAM_E_ARG and changes nothing. */
 int tcam_bbox_level_variant(int v);
-/* Profiling hook: device buffer of B * 16 uint64 receiving per-workgroup phase ticks of the
- * incremental level sweep (slots 0-7; slot 8 = levels processed), or NULL. */
+/* Profiling hook: device buffer of B * chunks * 16 uint64 (chunks = level ranges per frame)
+ * receiving per-workgroup phase ticks of the sorted-list level sweep (slots 0-7; slot 8 =
+ * levels processed, 9 = compression passes, 10 = full winner passes), or NULL. */
 int tcam_bbox_set_inc_debug(uint64_t* buf);
 
 /*

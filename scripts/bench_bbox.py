@@ -1,5 +1,5 @@
-"""Time the bbox kernels alone on the bench's CAMs (fill variants 2 = register lines,
-1 = LDS sweeps, 0 = clamp scans, the default); dump the CAMs for analysis.  Per-kernel
+"""Time the bbox kernels alone on the bench's CAMs (fill variants 1 = LDS sweeps,
+the cross-check, 0 = clamp scans, the default); dump the CAMs for analysis.  Per-kernel
 times: run it under rocprofv3 --kernel-trace --stats (scripts/gpu.sh bboxprof)."""
 import os
 import sys
@@ -23,7 +23,7 @@ os.makedirs("gpurun_out", exist_ok=True)
 np.save("gpurun_out/bench_cam_u8.npy", u8.cpu().numpy())
 from tcam_wsol_video_amd import _lib  # noqa: E402
 ref = None
-for variant in (2, 1, 0):
+for variant in (1, 0):
     _lib.load().tcam_bbox_fill_variant(variant)
     for _ in range(3):
         out = ops.bbox_levels(u8)

@@ -25,8 +25,8 @@ def main():
         valid = (torch.arange(256, device=dev)[None, :] < v[:, None])[..., None]
         return b * valid, v
 
-    ref = run(2, 1)
-    for fill, level in [(2, 1), (2, 2), (2, 0), (0, 1), (0, 2), (0, 0), (1, 0)]:
+    ref = run(1, 1)
+    for fill, level in [(1, 1), (1, 0), (0, 1), (0, 0)]:
         bad, where = 0, set()
         for _ in range(reps):
             b, v = run(fill, level)

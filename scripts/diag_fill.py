@@ -1,4 +1,5 @@
-"""Diagnostic: the fill stage's outputs (psi, level tables) of each fill variant on the same
+"""Diagnostic: the fill stage's outputs (psi, level tables) of the two fill variants (1 = LDS
+sweeps, the cross-check; 0 = clamp scans) on the same
 CAMs, read from the bbox workspace (tcam_bbox_levels with the per-level CCL sweep)."""
 import ctypes
 import os
@@ -19,7 +20,7 @@ def main():
     nws = lib.tcam_bbox_ws_bytes(B, H, W)
     lib.tcam_bbox_level_variant(1)
     outs = {}
-    for v in (2, 0):
+    for v in (1, 0):
         lib.tcam_bbox_fill_variant(v)
         if v == 0:
             lib.tcam_bbox_fill_variant(100 + int(os.environ.get("FILL_WAVES", "16")))
@@ -43,8 +44,8 @@ def main():
     lib.tcam_bbox_fill_variant(1000)
     lib.tcam_bbox_fill_variant(116)
     if len(sys.argv) > 2:
-        np.savez_compressed(sys.argv[2], psi2=outs[2][0], psi0=outs[0][0])
-    a, b = outs[2], outs[0]
+        np.savez_compressed(sys.argv[2], psi1=outs[1][0], psi0=outs[0][0])
+    a, b = outs[1], outs[0]
     for f in range(B):
         vm = a[4][f]
         dpsi = np.argwhere(a[0][f] != b[0][f])

@@ -17,7 +17,7 @@
 #   jpegprof             rocprofv3 --kernel-trace --stats of scripts/bench_jpeg.py -> gpurun_out/prof_jpeg/
 #   layererr             scripts/layer_error.py (per-layer error of x6 / f16x3 vs fp64) -> gpurun_out/layer_error.txt
 #   layers               scripts/layer_times.py r50 (per-launch conv times) -> gpurun_out/layer_times.txt
-#   incphases            scripts/diag_inc_phases.py for the incremental and the sorted-list sweeps
+#   incphases            scripts/diag_inc_phases.py: per-phase times of the sorted-list sweep
 #   bboxprof             rocprofv3 --kernel-trace --stats of scripts/bench_bbox.py -> gpurun_out/prof_bbox/
 #   bboxcost             scripts/diag_bbox_cost.py (headline loop with / without the bbox stage)
 #   tune                 scripts/tune_conv_x6.py (per-layer tile timings)
@@ -80,8 +80,7 @@ run_step() {
     timeout -k 10 300 python scripts/layer_times.py r50 > gpurun_out/layer_times.txt 2>&1
     rc=$?; head -12 gpurun_out/layer_times.txt; return $rc ;;
   incphases)
-    { TCAM_LEVEL_VARIANT=2 timeout -k 10 120 python scripts/diag_inc_phases.py &&
-      TCAM_LEVEL_VARIANT=0 timeout -k 10 120 python scripts/diag_inc_phases.py &&
+    { TCAM_LEVEL_VARIANT=0 timeout -k 10 120 python scripts/diag_inc_phases.py &&
       TCAM_BBOX_COMPRESS=0 TCAM_LEVEL_VARIANT=0 timeout -k 10 120 python scripts/diag_inc_phases.py &&
       TCAM_BBOX_INC_CHUNKS=1 TCAM_LEVEL_VARIANT=0 timeout -k 10 120 python scripts/diag_inc_phases.py; } > gpurun_out/inc_phases.txt 2>&1
     rc=$?; cat gpurun_out/inc_phases.txt | grep -v amdgpu.ids; return $rc ;;

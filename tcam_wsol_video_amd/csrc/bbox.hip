@@ -23,19 +23,37 @@
 // The oracle (oracle/contours.c, a restatement of the border follower) pins
 // this characterisation on random images in tests/test_bbox_oracle.py.
 //
-// Kernels:
-//  fill_kernel   one workgroup per frame: vmax = max(u8); psi by alternating
-//                row/column min-max sweeps to the fixpoint; histogram of psi
-//                -> the distinct levels (F_L only changes where psi = L + 1).
-//  level_kernel  one workgroup per (frame, chunk of distinct levels): psi in
-//                registers, per-level bitmap in LDS, block-based union-find
-//                (2x2 pixel blocks, 8-connectivity), run-based window-area
-//                accumulation into root slots, argmax with OpenCV's tie
-//                order, bbox.
-//  expand_kernel copies each canonical level's box to the levels it stands
-//                for.
-//  accumulate    one thread per (frame, tau): IoU vs GT (+1 inclusive
-//                convention, fp64) and the BoxEvaluator counters.
+// Two stages: the fill, one workgroup per frame (vmax = max(u8), psi, the
+// histogram of psi -> the distinct levels: F_L only changes where psi = L + 1),
+// and the level stage (the winning box of every distinct level).  Each has one
+// production kernel per frame size and one independent reference, which
+// tcam_bbox_fill_variant(1) / tcam_bbox_level_variant(1) select for the tests:
+//
+//   frame size   fill                            level stage
+//   <= 224^2     fill_scan_kernel                level_sorted_kernel
+//   <= 256^2     fill_scan_kernel                level_kernel<MAXH, MAXW, 2>
+//   <= 320^2     fill_kernel<BIGH, BIGP, false>  level_kernel<BIGH, BIGW, 4>
+//   reference    fill_kernel<MAXH, MAXP, true>   level_kernel
+//
+//  fill_scan_kernel     psi by row/column sweeps to the fixpoint, every line
+//                       sweep a wave-parallel scan of composed clamps; also
+//                       writes the psi-sorted pixel list of the sorted sweep.
+//  fill_kernel          the same sweeps, one thread per line walking it in LDS;
+//                       frames above 256^2 keep the u8 image in global memory
+//                       so that psi alone fits in LDS.
+//  level_sorted_kernel  walks a frame's levels from the top, adding each level's
+//                       new pixels (a slice of the sorted list) to a union-find
+//                       over 2x2 blocks whose roots carry area, first pixel and
+//                       box; the winner is searched among the touched roots.
+//  level_kernel         one workgroup per (frame, chunk of distinct levels), each
+//                       level from scratch: psi in registers, per-level bitmap in
+//                       LDS, block-based union-find (2x2 pixel blocks,
+//                       8-connectivity), run-based window-area accumulation into
+//                       root slots, argmax with OpenCV's tie order, bbox.
+//  expand_kernel        copies each canonical level's box to the levels it stands
+//                       for.
+//  accumulate_kernel    one thread per (frame, tau): IoU vs GT (+1 inclusive
+//                       convention, fp64) and the BoxEvaluator counters.
 #include "common.h"
 
 namespace {
@@ -50,12 +68,15 @@ constexpr int DBG_SLOTS = 16;   // per-workgroup phase-time slots (tcam_bbox_set
 uint64_t* g_dbg = nullptr;
 int g_fill_waves = NTB / 64;   // (debug) waves sweeping lines in fill_scan_kernel
 int g_fill_maxit = 1 << 30;    // (debug) row + column passes at most
-int g_fill_variant = 0;  // 0 = clamp-scan fill (default), 1 = LDS sweep fill, 2 = register lines
-int g_level_variant = 0;
+int g_fill_variant = 0;  // 0 = clamp-scan fill (default), 1 = LDS sweep fill (the cross-check)
+int g_level_variant = 0;  // 0 = sorted-list sweep where it applies, 1 = level_kernel always
 int g_bbox_chunks = 0;   // level ranges per frame for the next calls (0: the default)
-uint64_t* g_inc_dbg = nullptr;  // per-WG phase ticks of level_inc_kernel (profiling)
+uint64_t* g_inc_dbg = nullptr;  // per-WG phase ticks of level_sorted_kernel (profiling)
 
 __device__ inline uint64_t rt() { return __builtin_amdgcn_s_memrealtime(); }
+// Phase timer of the two level kernels (locals dbg, ph[8], tp): with a debug buffer, the ticks
+// since the previous call are added to ph[k].
+#define PHASE(k) do { if (dbg) { uint64_t t_ = rt(); ph[k] += t_ - tp; tp = t_; } } while (0)
 
 __host__ __device__ inline int pitch_of(int W) {
     int d = (W + 3) / 4;
@@ -77,9 +98,6 @@ __device__ inline int block_max_i(int v, int* red) {
     }
     __syncthreads();
     return red[NTB / 64];
-}
-__device__ inline int block_min_i(int v, int* red) {
-    return -block_max_i(-v, red);
 }
 
 // ------------------------------------------------------- sorted pixel list
@@ -336,202 +354,8 @@ __global__ __launch_bounds__(NTB) void fill_kernel(const uint8_t* __restrict__ c
     if (slist) emit_sorted(psi, P, hist, cur, H, W, b, slist, cgt);
 }
 
-// ------------------------------------------------------- fill (registers)
-// Same result as fill_kernel, one 256-thread workgroup per frame (one thread
-// per row, then per column).  A line of psi and u8 lives in VGPRs, packed 4
-// pixels per dword (<= 64 dwords each), so a sweep step is a register chain:
-// psi <- max(u, min(psi, prev)) == med3(prev, u, psi) because psi >= u holds
-// from the initialisation (255) on.  LDS only carries lines between the row
-// and column phases.
-constexpr int NTF = 256;
-
-// Forward then backward sweep over a packed line of LDN dwords; pixels past
-// the line end are u = psi = 0, which acts exactly like the outside (-1) for
-// the backward pass and is never read back.  Returns whether anything changed.
-template <int LDN>
-__device__ __forceinline__ bool sweep_line(uint32_t (&pl)[LDN], const uint32_t (&ul)[LDN]) {
-    uint32_t diff = 0;
-    int prev = -1;
-#pragma unroll
-    for (int d = 0; d < LDN; ++d) {
-        const uint32_t w = pl[d];
-        uint32_t uw = ul[d];
-        asm volatile("" : "+v"(uw));  // opaque: byte extracts not shared across passes
-        const int n0 = max((int)(uw & 255u), min((int)(w & 255u), prev));
-        const int n1 = max((int)((uw >> 8) & 255u), min((int)((w >> 8) & 255u), n0));
-        const int n2 = max((int)((uw >> 16) & 255u), min((int)((w >> 16) & 255u), n1));
-        const int n3 = max((int)(uw >> 24), min((int)(w >> 24), n2));
-        prev = n3;
-        uint32_t o = (uint32_t)n0 | ((uint32_t)n1 << 8) | ((uint32_t)n2 << 16) |
-                     ((uint32_t)n3 << 24);
-        asm volatile("" : "+v"(o));  // opaque: no n0..n3 kept alive for the other pass
-        diff |= o ^ w;
-        pl[d] = o;
-        __builtin_amdgcn_sched_barrier(0);  // keep the chain in order (no hoisted extracts)
-    }
-    prev = -1;
-#pragma unroll
-    for (int d = LDN - 1; d >= 0; --d) {
-        const uint32_t w = pl[d];
-        uint32_t uw = ul[d];
-        asm volatile("" : "+v"(uw));  // opaque: byte extracts not shared across passes
-        const int n3 = max((int)(uw >> 24), min((int)(w >> 24), prev));
-        const int n2 = max((int)((uw >> 16) & 255u), min((int)((w >> 16) & 255u), n3));
-        const int n1 = max((int)((uw >> 8) & 255u), min((int)((w >> 8) & 255u), n2));
-        const int n0 = max((int)(uw & 255u), min((int)(w & 255u), n1));
-        prev = n0;
-        uint32_t o = (uint32_t)n0 | ((uint32_t)n1 << 8) | ((uint32_t)n2 << 16) |
-                     ((uint32_t)n3 << 24);
-        asm volatile("" : "+v"(o));  // opaque: no n0..n3 kept alive for the other pass
-        diff |= o ^ w;
-        pl[d] = o;
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    return diff != 0;
-}
-
-template <int LDN>
-__global__ __launch_bounds__(NTF) void fill_reg_kernel(const uint8_t* __restrict__ cam_u8,
-                                                       uint8_t* __restrict__ psi_out,
-                                                       int32_t* __restrict__ vmax_out,
-                                                       int32_t* __restrict__ canon,
-                                                       int32_t* __restrict__ lev_list,
-                                                       int32_t* __restrict__ nlev, int H, int W,
-                                                       uint64_t* __restrict__ dbg,
-                                                       uint16_t* __restrict__ slist,
-                                                       int32_t* __restrict__ cgt) {
-    const uint64_t t0 = rt();
-    __shared__ uint8_t img[MAXH * MAXP];
-    __shared__ uint8_t psi[MAXH * MAXP];
-    __shared__ int red[NTF / 64 + 1];
-    __shared__ int hist[257];
-    __shared__ int cur[257];
-    __shared__ int changed;
-    const int b = blockIdx.x;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wid = tid >> 6;
-    const int P = pitch_of(W);  // >= 4 * LDN is not required: row dwords past W are padding
-    const uint8_t* src = cam_u8 + (long)b * H * W;
-    int vm = 0;
-    for (int i = tid; i < H * W; i += NTF) {
-        const int y = i / W, x = i - y * W;
-        const uint8_t v = src[i];
-        img[y * P + x] = v;
-        vm = max(vm, (int)v);
-    }
-    // zero the row padding bytes [W, 4*ceil(W/4)) that the packed rows read
-    for (int i = tid; i < H * 4; i += NTF) {
-        const int y = i >> 2, x = W + (i & 3);
-        if (x < ((W + 3) & ~3)) img[y * P + x] = 0;
-    }
-    vm = wave_max_i(vm);
-    if (lane == 0) red[wid] = vm;
-    __syncthreads();
-    vm = max(max(red[0], red[1]), max(red[2], red[3]));
-    if (tid == 0) vmax_out[b] = vm;
-    const uint64_t t1 = rt();
-
-    uint32_t pl[LDN], ul[LDN];
-    const int ndw = (W + 3) >> 2;  // dwords of a row
-    const int ndh = (H + 3) >> 2;  // dwords of a column
-    int iters = 0;
-    bool first = true;
-    for (;;) {
-        bool ch = false;
-        // ---- rows: thread y
-        if (tid < H) {
-            const uint32_t* irow = reinterpret_cast<const uint32_t*>(img + tid * P);
-            uint32_t* prow = reinterpret_cast<uint32_t*>(psi + tid * P);
-#pragma unroll
-            for (int d = 0; d < LDN; ++d) {
-                const bool in = d < ndw;
-                ul[d] = in ? irow[d] : 0u;
-                pl[d] = in ? (first ? 0xFFFFFFFFu : prow[d]) : 0u;
-            }
-            if (first) {  // padding pixels of the last dword are 0, not 255
-#pragma unroll
-                for (int d = 0; d < LDN; ++d)
-                    if (d == ndw - 1 && (W & 3)) pl[d] &= (1u << (8 * (W & 3))) - 1u;
-            }
-            const bool m = sweep_line<LDN>(pl, ul);
-            ch |= m;
-            if (m || first) {
-#pragma unroll
-                for (int d = 0; d < LDN; ++d)
-                    if (d < ndw) prow[d] = pl[d];
-            }
-        }
-        first = false;
-        __syncthreads();
-        // ---- columns: thread x (bytes gathered into packed registers)
-        if (tid < W) {
-#pragma unroll
-            for (int d = 0; d < LDN; ++d) {
-                uint32_t pw = 0, uw = 0;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int y = 4 * d + e;
-                    if (y < H) {
-                        pw |= (uint32_t)psi[y * P + tid] << (8 * e);
-                        uw |= (uint32_t)img[y * P + tid] << (8 * e);
-                    }
-                }
-                pl[d] = pw;
-                ul[d] = uw;
-                if ((d & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // bound loads in flight
-            }
-            const bool m = sweep_line<LDN>(pl, ul);
-            ch |= m;
-            if (m) {
-#pragma unroll
-                for (int d = 0; d < LDN; ++d)
-                    if (d < ndh) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const int y = 4 * d + e;
-                            if (y < H) psi[y * P + tid] = (uint8_t)(pl[d] >> (8 * e));
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-            }
-        }
-        if (tid == 0) changed = 0;
-        __syncthreads();
-        if (ch) changed = 1;  // benign same-value race
-        __syncthreads();
-        ++iters;
-        if (!__builtin_amdgcn_readfirstlane(changed)) break;
-    }
-    const uint64_t t2 = rt();
-    uint8_t* dst = psi_out + (long)b * H * W;
-    for (int i = tid; i < 257; i += NTF) hist[i] = 0;
-    __syncthreads();
-    for (int i = tid; i < H * W; i += NTF) {
-        const int y = i / W, x = i - y * W;
-        const uint8_t v = psi[y * P + x];
-        dst[i] = v;
-        atomicAdd(&hist[v], 1);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int n = 0, next = vm - 1;
-        for (int L = vm - 1; L >= 0; --L) {
-            if (hist[L + 1] > 0) next = L;
-            canon[b * 256 + L] = next;
-        }
-        for (int L = 0; L < vm; ++L)
-            if (hist[L + 1] > 0) lev_list[b * 256 + n++] = L;
-        nlev[b] = n;
-        if (dbg) {
-            uint64_t* d = dbg + (long)b * DBG_SLOTS;
-            d[0] = t1 - t0; d[1] = t2 - t1; d[2] = rt() - t2; d[3] = iters; d[4] = n;
-        }
-    }
-    if (slist) emit_sorted(psi, P, hist, cur, H, W, b, slist, cgt);
-}
-
 // ------------------------------------------------------- fill (clamp scans)
-// Same psi as fill_reg_kernel, with every line sweep a wave-parallel scan.  A sweep step
+// Same psi as fill_kernel, with every line sweep a wave-parallel scan.  A sweep step
 // x_i = max(u_i, min(psi_i, x_{i-1})) clamps x_{i-1} to [u_i, psi_i] (psi >= u always), and
 // clamps compose into clamps: clamp[a2,b2] o clamp[a1,b1] = clamp[c(a1), c(b1)] with
 // c = clamp[a2,b2].  So a line of <= 256 pixels is 4 pixels per lane: each lane composes its
@@ -902,7 +726,6 @@ __global__ __launch_bounds__(NTB) void level_kernel(const uint8_t* __restrict__ 
                                                     uint64_t* __restrict__ dbg) {
     uint64_t ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t tp = rt();
-#define PHASE(k) do { if (dbg) { uint64_t t_ = rt(); ph[k] += t_ - tp; tp = t_; } } while (0)
     __shared__ uint32_t bm[LH * (LW / 32)];
     __shared__ uint32_t lab[(LH / 2) * (LW / 2)];
     __shared__ int red[4 * (NTB / 64) + 4];
@@ -1171,7 +994,6 @@ __global__ __launch_bounds__(NTB) void level_kernel(const uint8_t* __restrict__ 
         uint64_t* d = dbg + (long)(gridDim.x + blockIdx.x) * DBG_SLOTS;
         for (int k = 0; k < 7; ++k) d[k] = ph[k];
     }
-#undef PHASE
 }
 
 // Fill the rows of non-canonical levels from their canonical level.
@@ -1233,29 +1055,39 @@ __global__ void accumulate_kernel(const int32_t* __restrict__ boxes,
     }
 }
 
-
-// ---- incremental level sweep (frames <= 224 x 224).  The level sets F_L = {psi > L} are
-// nested: going down the listed levels only ADDS pixels, so components only grow and merge.
-// A workgroup takes a contiguous range of one frame's levels (INC_CHUNKS ranges per frame)
-// and walks it from the top, keeping across levels, per 2x2 block: the union-find parent
-// (hooked toward the smaller block index, so a root is its component's first block), and
-// per root the window area in half units and the raster index of the first pixel.  Per
-// level only the new pixels are visited: their blocks join, they unite with their set
-// 8-neighbours, roots hooked this level pass their area/key on, and every 2x2 window that
-// holds a new pixel adds contrib(new count) - contrib(old count) (processed once, by its
-// first new pixel).  Window areas are additive because all set pixels of a window are
-// 8-adjacent (one component).  The winner is max(area, then key) — the same as level_kernel
-// (largest area, ties to the last first-pixel in raster order = the first contour in
-// OpenCV's list) — taken over the roots TOUCHED this level only (roots of the new pixels,
-// roots that took a hooked root in, the previous winner's root): every other root kept its
-// value, which was below the previous winner's.  Only when the new maximum is below the
-// previous winner's value (its key fell with no area gain) does a full pass over the roots
-// decide.  The bounding box grows the previous box by the winner's new pixels when the
-// winner is the previous winner root and absorbed no earlier-set pixels; otherwise one pass
-// over the blocks takes it (and compresses every path).  Hooked roots are listed by
-// unite_pk, so no step scans all blocks on a level that keeps its winner.  The per-block
-// parent and first-pixel key share one word (parent-key words, see pk below), which leaves
-// room in LDS for the level's new-pixel list.
+// ---- sorted-list level sweep (frames <= 224 x 224, default).  The level sets F_L = {psi > L}
+// are nested: going down the listed levels only ADDS pixels, so components only grow and
+// merge.  A workgroup takes a contiguous range of one frame's levels (INC_CHUNKS ranges per
+// frame) and walks it from the top; the pixels new at a level are a slice of the frame's pixel
+// list sorted by psi (the fill writes it, emit_sorted), so no level thresholds psi or compacts
+// a list — the slice sets its bits in the level bitmaps and stages itself in LDS (the range's
+// first level takes every pixel above it).  Kept across levels:
+//  * per 2x2 block (all its set pixels are 8-adjacent, so block labels are pixel labels) the
+//    union-find parent, hooked toward the smaller block index: a root is its component's first
+//    block in raster order;
+//  * per root the raster index of its component's first pixel, the key.  Parent and key share
+//    one word (pk = parent << 16 | key; key 0xFFFF on non-roots and on roots that hold no pixel
+//    yet; INACT = block not active), so the hook that makes a root a child, an atomicMin with
+//    key 0xFFFF, also clears its key and returns it for the handover;
+//  * per root the window area in half units (the shoelace area of the header comment).  Window
+//    areas are additive over components because all set pixels of a 2x2 window are 8-adjacent
+//    (one component): every window that holds a new pixel adds contrib(new count) -
+//    contrib(old count), once, by its first new pixel in raster order;
+//  * per root its component's bounding box (x0, x1 in xr, y1 in the top byte of its area word,
+//    y0 = key / W), widened by its new pixels and merged on a hook, so the winner's box is read
+//    off its root: no pass over the blocks, whatever merged.
+// Per level only the new pixels are visited: their blocks become active, they unite with the
+// blocks of their set 8-neighbours, and the roots hooked this level — unite_pk lists them, so
+// no step scans all blocks to find them — pass their area, key and box on to their new root.
+// The winner is max(area, then key) — the same as level_kernel (largest area, ties to the last
+// first-pixel in raster order = the first contour in OpenCV's list) — taken over the roots
+// TOUCHED this level only (roots of the new pixels, roots that took a hooked root in, the
+// previous winner's root): every other root kept its value, which was below the previous
+// winner's.  Only when the new maximum is below the previous winner's value (its key fell with
+// no area gain) does a full pass over the roots decide.
+// Paths are compressed only where the winner search walks them (the touched blocks); a
+// compression pass over all blocks on the merge levels measured slower than the longer paths it
+// saves (TCAM_BBOX_COMPRESS=1).
 // Bit-identical to level_kernel (tests/test_gpu_ops.py).
 // One range per frame (the whole level list in one workgroup) by default: a workgroup holds
 // a CU's whole LDS, so the side stream's cost to the pipelined forward is its CU-time, and a
@@ -1265,31 +1097,11 @@ __global__ void accumulate_kernel(const int32_t* __restrict__ boxes,
 constexpr int INC_CHUNKS = 1;      // default level ranges per frame
 constexpr int INC_MAX_CHUNKS = 4;  // workspace is sized for this many
 constexpr int IH = 224, IW = 224, IWPR = 7, IBW = 112, INB = IBW * (IH / 2);
+constexpr int SCAP = INB;                          // new-pixel entries staged in LDS
+constexpr uint32_t SAMASK = (1u << 17) - 1;        // ar word: area (half units) | y1 << 24
+constexpr uint32_t XR_EMPTY = 0x00FFu;             // xr half-word: x0 | x1 << 8; empty box
 
-__device__ inline unsigned long long block_max_u64(unsigned long long v,
-                                                   unsigned long long* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long t = __shfl_xor(v, o, 64);
-        v = t > v ? t : v;
-    }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long m = red[0];
-        for (int i = 1; i < NTB / 64; ++i) m = red[i] > m ? red[i] : m;
-        red[NTB / 64] = m;
-    }
-    __syncthreads();
-    return red[NTB / 64];
-}
-
-constexpr int32_t AFLAG = 1 << 30, AMASK = AFLAG - 1;  // area word: flag | half units
-constexpr int LCAP = INB * 2;   // new-pixel list entries held in LDS (uint16)
-
-// parent-key words (level_inc_kernel): parent in the high half
+// parent-key words: parent in the high half
 __device__ inline uint32_t find_root_pk(const uint32_t* pk, uint32_t x) {
     uint32_t p = pk[x] >> 16;
     while (p != x) {
@@ -1319,343 +1131,6 @@ __device__ inline void unite_pk(uint32_t* pk, uint32_t a, uint32_t b, uint32_t* 
 }
 
 __device__ inline int win_contrib(int c) { return c == 4 ? 2 : (c == 3 ? 1 : 0); }
-
-__global__ __launch_bounds__(NTB) void level_inc_kernel(const uint8_t* __restrict__ psi_g,
-                                                        const int32_t* __restrict__ lev_list,
-                                                        const int32_t* __restrict__ nlev,
-                                                        int32_t* __restrict__ boxes, int H,
-                                                        int W, uint32_t* __restrict__ plist_g,
-                                                        uint32_t* __restrict__ hlist_g,
-                                                        uint64_t* __restrict__ dbg, int nch) {
-    uint64_t ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint32_t n_full = 0, n_fallback = 0;   // (debug) full bbox scans, full winner passes
-    uint64_t tp = rt();
-#define IPHASE(k) do { if (dbg) { uint64_t t_ = rt(); ph[k] += t_ - tp; tp = t_; } } while (0)
-    __shared__ uint32_t bm[IH * IWPR];    // F at the current level
-    __shared__ uint32_t db[IH * IWPR];    // pixels new at the current level
-    // per block: parent << 16 | key (key = raster index of the component's first pixel,
-    // kept by roots; 0xFFFF on non-roots and on roots that hold no pixel yet; INACT = not
-    // active).  One word, so the hook that makes a root a child (atomicMin with key 0xFFFF)
-    // also clears its key and returns it for the handover.
-    __shared__ uint32_t pk[INB];
-    __shared__ int32_t area[INB];         // per root: window area, half units
-    __shared__ uint16_t lst[LCAP];        // this level's new pixels (y << 8 | x), if they fit
-    __shared__ unsigned long long redl[NTB / 64 + 1];
-    __shared__ int red[4 * (NTB / 64) + 4];
-    __shared__ int wsum[NTB / 64 + 1];
-    __shared__ int s_nhook;               // roots hooked this level (hlist entries)
-    __shared__ unsigned long long s_pbest;  // the previous winner's (area, key) value
-    const int b = blockIdx.x / nch, chunk = blockIdx.x % nch;
-    // the list of a level with more than LCAP new pixels goes to global scratch
-    uint32_t* plist = plist_g + (long)blockIdx.x * IH * IW;
-    uint32_t* hlist = hlist_g + (long)blockIdx.x * INB;   // this level's hooked roots
-    const int nl = __builtin_amdgcn_readfirstlane(nlev[b]);   // (scalar: loop bound)
-    const int l0 = nl * chunk / nch, l1 = nl * (chunk + 1) / nch;
-    if (l0 >= l1) return;
-    const int wpr = (W + 31) / 32, NW = H * wpr;
-    const int BW = (W + 1) / 2, BH = (H + 1) / 2, NB = BH * BW;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    constexpr int QW = 2;   // bitmap words per thread (224 x 7 <= 2 x 1024)
-
-    uint32_t pv[QW][8];
-    const uint8_t* src = psi_g + (long)b * H * W;
-#pragma unroll
-    for (int q = 0; q < QW; ++q) {
-        const int w = tid + q * NTB;
-#pragma unroll
-        for (int d = 0; d < 8; ++d) pv[q][d] = 0u;
-        if (w < NW) {
-            const int y = w / wpr, x0 = (w - y * wpr) * 32;
-#pragma unroll
-            for (int d = 0; d < 8; ++d) {
-                uint32_t v = 0;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int x = x0 + 4 * d + e;
-                    if (x < W) v |= (uint32_t)src[y * W + x] << (8 * e);
-                }
-                pv[q][d] = v;
-            }
-        }
-    }
-    for (int i = tid; i < NB; i += NTB) {
-        pk[i] = INACT;
-        area[i] = 0;
-    }
-    if (tid == 0) s_pbest = 0;
-    uint32_t ob[QW] = {0u, 0u};
-    LevelCtx cx{bm, H, W, wpr, BW};
-    uint32_t pwin = INACT;                 // previous level's winner root
-    int bx0 = 0, by0 = 0, bx1 = 0, by1 = 0;  // and its pixel box (thread 0)
-    auto isnew = [&](int y, int x) -> int {
-        if ((unsigned)y >= (unsigned)H || (unsigned)x >= (unsigned)W) return 0;
-        return (db[y * wpr + (x >> 5)] >> (x & 31)) & 1;
-    };
-
-    for (int li = l1 - 1; li >= l0; --li) {
-        const int L = lev_list[b * 256 + li];
-        uint32_t nb[QW], df[QW];
-#pragma unroll
-        for (int q = 0; q < QW; ++q) {
-            const int w = tid + q * NTB;
-            uint32_t bits = 0;
-#pragma unroll
-            for (int d = 0; d < 8; ++d)
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    bits |= (uint32_t)(((pv[q][d] >> (8 * e)) & 255u) > (uint32_t)L) << (4 * d + e);
-            nb[q] = w < NW ? bits : 0u;
-            df[q] = nb[q] & ~ob[q];
-            if (w < NW) {
-                bm[w] = nb[q];
-                db[w] = df[q];
-            }
-        }
-        // compact list of the new pixels: block-wide exclusive prefix sum of the counts
-        int cnt = __builtin_popcount(df[0]) + __builtin_popcount(df[1]);
-        int incl = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += t;
-        }
-        if (lane == 63) wsum[wid] = incl;
-        __syncthreads();
-        if (tid == 0) {
-            s_nhook = 0;
-            int acc = 0;
-            for (int i = 0; i < NTB / 64; ++i) {
-                const int t = wsum[i];
-                wsum[i] = acc;
-                acc += t;
-            }
-            wsum[NTB / 64] = acc;
-        }
-        __syncthreads();
-        const int nnew = wsum[NTB / 64];
-        const bool inl = nnew <= LCAP;   // (block-uniform) the list fits in LDS
-        {
-            int pos = wsum[wid] + incl - cnt;
-#pragma unroll
-            for (int q = 0; q < QW; ++q) {
-                uint32_t bits = df[q];
-                const int w = tid + q * NTB, y = w / wpr, xb = (w - y * wpr) * 32;
-                while (bits) {
-                    const int x = xb + __builtin_ctz(bits);
-                    bits &= bits - 1;
-                    if (inl) lst[pos++] = (uint16_t)(y << 8 | x);
-                    else plist[pos++] = (uint32_t)(y << 8 | x);
-                }
-            }
-        }
-        __syncthreads();   // list written (a global one is read back past the L1: volatile)
-        const volatile uint32_t* plv = plist;
-        auto newpx = [&](int it) -> uint32_t { return inl ? (uint32_t)lst[it] : plv[it]; };
-        IPHASE(0);
-        // 1. blocks of new pixels become active (roots of themselves); a block, once
-        // active, stays active (F only grows)
-        // (new pixels cluster along the region's boundary, so they are dealt to threads
-        // pixel by pixel, consecutive pixels to consecutive lanes, not word by word)
-        for (int it = tid; it < nnew; it += NTB) {
-            const uint32_t pp = newpx(it);
-            const int y = (int)(pp >> 8), x = (int)(pp & 255);
-            const uint32_t blk = (y >> 1) * BW + (x >> 1);
-            if (pk[blk] == INACT) pk[blk] = blk << 16 | 0xFFFFu;
-        }
-        __syncthreads();
-        IPHASE(1);
-        // 2. new pixels unite their block with the blocks of their set 8-neighbours
-        // (one lane per (pixel, neighbour): eight short union chains in parallel rather
-        // than one chain of eight)
-        for (int it = tid; it < nnew * 8; it += NTB) {
-            const uint32_t pp = newpx(it >> 3);
-            const int y = (int)(pp >> 8), x = (int)(pp & 255);
-            const int d = (it & 7) + ((it & 7) >= 4);   // 0..8 without the centre
-            const int dy = d / 3 - 1, dx = d % 3 - 1;
-            if (!cx.bit(y + dy, x + dx)) continue;
-            const uint32_t blk = (y >> 1) * BW + (x >> 1);
-            const uint32_t nbk = ((y + dy) >> 1) * BW + ((x + dx) >> 1);
-            if (nbk != blk) unite_pk(pk, blk, nbk, hlist, &s_nhook);
-        }
-        __syncthreads();
-        IPHASE(2);
-        // 3. roots hooked this level (hlist: block << 16 | its key before the hook) hand
-        // their area / key to their new root
-        const int nhook = s_nhook;
-        const volatile uint32_t* hlv = hlist;
-        for (int it = tid; it < nhook; it += NTB) {
-            const uint32_t e = hlv[it], i = e >> 16, k = e & 0xFFFFu;
-            if (k != 0xFFFFu) {
-                const uint32_t r = find_root_pk(pk, i);
-                // flag: r now holds pixels that were set before this level outside the
-                // tree it had (the winner's bbox cannot be extended from new pixels alone)
-                atomicAdd(&area[r], area[i] & AMASK);
-                atomicOr(&area[r], AFLAG);
-                atomicMin(&pk[r], r << 16 | k);
-                area[i] = 0;
-            }
-        }
-        // (no barrier: step 4 only adds into current roots, which step 3 never clears,
-        // and the additions commute)
-        IPHASE(3);
-        // 4. first pixels and window-area deltas of the new pixels
-        // (one lane per (pixel, window))
-        for (int it = tid; it < nnew * 4; it += NTB) {
-            const uint32_t pp = newpx(it >> 2);
-            const int y = (int)(pp >> 8), x = (int)(pp & 255);
-            {
-                const uint32_t r = find_root_pk(pk, (y >> 1) * BW + (x >> 1));
-                if ((it & 3) == 0) atomicMin(&pk[r], r << 16 | (uint32_t)(y * W + x));
-                int dsum = 0;
-                {
-                    const int wy = y - 1 + ((it >> 1) & 1), wx = x - 1 + (it & 1);
-                    {
-                        int cn = 0, co = 0;
-                        bool owner = true;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const int qy = wy + (k >> 1), qx = wx + (k & 1);
-                            const int nbit = cx.bit(qy, qx), nw = isnew(qy, qx);
-                            cn += nbit;
-                            co += nbit & (nw ^ 1);
-                            // an earlier (raster order) new pixel of this window owns it
-                            if (nw && (qy < y || (qy == y && qx < x))) owner = false;
-                        }
-                        if (owner) dsum += win_contrib(cn) - win_contrib(co);
-                    }
-                }
-                if (dsum) atomicAdd(&area[r], dsum);
-            }
-        }
-        __syncthreads();
-        IPHASE(4);
-#pragma unroll
-        for (int q = 0; q < QW; ++q) ob[q] = nb[q];
-        // 5. the winner over the touched roots (each touched block's path is compressed on
-        // the way: no unites run in this step, and a non-root re-pointed at its root keeps
-        // every find_root correct)
-        unsigned long long best = 0;
-        auto cand = [&](uint32_t x) {
-            const uint32_t r = find_root_pk(pk, x);
-            if (r != x) pk[x] = r << 16 | 0xFFFFu;
-            const unsigned long long a =
-                ((unsigned long long)(uint32_t)(area[r] & AMASK) << 32) | (pk[r] & 0xFFFFu);
-            best = a > best ? a : best;
-        };
-        for (int it = tid; it < nnew; it += NTB) {
-            const uint32_t pp = newpx(it);
-            cand(((pp >> 8) >> 1) * BW + ((pp & 255) >> 1));
-        }
-        for (int it = tid; it < nhook; it += NTB) cand(hlv[it] >> 16);
-        if (tid == 0 && pwin != INACT) cand(pwin);
-        IPHASE(5);
-        best = block_max_u64(best, redl);
-        if (__builtin_amdgcn_readfirstlane((int)(best < s_pbest))) {
-            ++n_fallback;
-            // the previous winner's value fell (its key dropped with no area gain): an
-            // untouched root may now lead, so every root decides
-            best = 0;
-            for (int i = tid; i < NB; i += NTB) {
-                const uint32_t v = pk[i];
-                if ((v >> 16) == (uint32_t)i) {
-                    const unsigned long long a =
-                        ((unsigned long long)(uint32_t)(area[i] & AMASK) << 32) | (v & 0xFFFFu);
-                    best = a > best ? a : best;
-                }
-            }
-            best = block_max_u64(best, redl);
-        }
-        const uint32_t fp = (uint32_t)best;
-        const uint32_t wb = ((fp / W) >> 1) * BW + ((fp % W) >> 1);
-        const uint32_t wroot = find_root_pk(pk, wb);
-        IPHASE(6);
-        // 7. its bounding box.  F only grows, so when the winner is the previous level's
-        // winner root and took in no earlier-set pixels through a merge (no flag), its
-        // box is the previous box grown by its new pixels; otherwise scan every block.
-        const bool grow = wroot == pwin && !(area[wroot] & AFLAG);
-        n_full += grow ? 0 : 1;
-        int x0 = W, y0 = H, x1 = -1, y1 = -1;
-        if (grow) {
-            for (int it = tid; it < nnew; it += NTB) {
-                const uint32_t pp = newpx(it);
-                const int y = (int)(pp >> 8), x = (int)(pp & 255);
-                if ((pk[(y >> 1) * BW + (x >> 1)] >> 16) != wroot) continue;
-                x0 = min(x0, x); x1 = max(x1, x);
-                y0 = min(y0, y); y1 = max(y1, y);
-            }
-            if (tid == 0) {
-                x0 = min(x0, bx0); y0 = min(y0, by0);
-                x1 = max(x1, bx1); y1 = max(y1, by1);
-            }
-        } else
-        for (int i = tid; i < NB; i += NTB) {
-            // (compresses every path on the way, see step 5)
-            const uint32_t w = pk[i];
-            if (w == INACT) continue;
-            const uint32_t v = w >> 16;
-            const uint32_t r = v == (uint32_t)i ? v : find_root_pk(pk, i);
-            if (r != v) pk[i] = r << 16 | 0xFFFFu;
-            if (r != wroot) continue;
-            const int by = i / BW, x = 2 * (i - by * BW), y = 2 * by;
-            const int top = cx.pair(y, x), bot = cx.pair(y + 1, x);
-            if (top | bot) {
-                x0 = min(x0, ((top | bot) & 1) ? x : x + 1);
-                x1 = max(x1, ((top | bot) & 2) ? x + 1 : x);
-                y0 = min(y0, top ? y : y + 1);
-                y1 = max(y1, bot ? y + 1 : y);
-            }
-        }
-        x0 = wave_min_i(x0); y0 = wave_min_i(y0);
-        x1 = wave_max_i(x1); y1 = wave_max_i(y1);
-        if (lane == 0) {
-            red[4 * wid + 0] = x0; red[4 * wid + 1] = y0;
-            red[4 * wid + 2] = x1; red[4 * wid + 3] = y1;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < NTB / 64; ++w) {
-                x0 = min(x0, red[4 * w + 0]); y0 = min(y0, red[4 * w + 1]);
-                x1 = max(x1, red[4 * w + 2]); y1 = max(y1, red[4 * w + 3]);
-            }
-            int32_t* box = boxes + ((long)b * 256 + L) * 4;
-            box[0] = x0;
-            box[1] = y0;
-            box[2] = min(x1 + 1, W - 1);  // boundingRect x + w, clamped (wsol_metrics.py:175-178)
-            box[3] = min(y1 + 1, H - 1);
-            bx0 = x0; by0 = y0; bx1 = x1; by1 = y1;
-            area[wroot] &= AMASK;   // every thread has read the flag (barrier above)
-            s_pbest = best;         // and s_pbest
-        }
-        pwin = wroot;
-        __syncthreads();
-        IPHASE(7);
-    }
-    if (dbg && tid == 0) {
-        uint64_t* d = dbg + (long)blockIdx.x * DBG_SLOTS;
-        for (int k = 0; k < 8; ++k) d[k] = ph[k];
-        d[8] = l1 - l0;
-        d[9] = n_full;
-        d[10] = n_fallback;
-    }
-#undef IPHASE
-}
-
-// ---- sorted-list level sweep (frames <= 224 x 224, default).  The incremental sweep above,
-// with two changes that remove its two full-frame passes per level:
-//  * the new pixels of a level are a slice of the frame's pixel list sorted by psi (the fill
-//    writes it, emit_sorted): no threshold pass over psi and no block-wide compaction — the
-//    slice sets its bits in the level bitmaps and stages itself in LDS;
-//  * every root keeps its component's bounding box (x0, x1 in xr, y1 in the top byte of its
-//    area word, y0 = key / W), widened by its new pixels (one CAS per root per wave) and
-//    merged on a hook, so the winner's box is read off its root: no bbox scan over the blocks,
-//    whatever merged.
-// Paths are compressed only where the winner search walks them (the touched blocks); a
-// compression pass over all blocks on the merge levels (what the full bbox scans used to
-// provide) measured slower than the longer paths it saves (TCAM_BBOX_COMPRESS=1).
-// Bit-identical to level_kernel (tests/test_gpu_ops.py).
-constexpr int SCAP = INB;                          // new-pixel entries staged in LDS
-constexpr uint32_t SAMASK = (1u << 17) - 1;        // ar word: area (half units) | y1 << 24
-constexpr uint32_t XR_EMPTY = 0x00FFu;             // xr half-word: x0 | x1 << 8; empty box
 
 __device__ inline uint32_t lds_ld(const uint32_t* p) { return *(const volatile uint32_t*)p; }
 
@@ -1709,10 +1184,9 @@ __global__ __launch_bounds__(NTB) void level_sorted_kernel(
     uint64_t ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t n_comp = 0, n_fallback = 0;   // (debug) compression passes, full winner passes
     uint64_t tp = rt();
-#define SPHASE(k) do { if (dbg) { uint64_t t_ = rt(); ph[k] += t_ - tp; tp = t_; } } while (0)
     __shared__ uint32_t bm[IH * IWPR];    // F at the current level
     __shared__ uint32_t db[IH * IWPR];    // pixels new at the current level
-    __shared__ uint32_t pk[INB];          // parent << 16 | key, as level_inc_kernel
+    __shared__ uint32_t pk[INB];          // parent << 16 | key
     __shared__ uint32_t ar[INB];          // per root: area (half units) | y1 << 24
     __shared__ uint32_t xr[INB / 2];      // per root: x0 | x1 << 8 (uint16 pairs)
     __shared__ uint16_t lst[SCAP];        // this level's new pixels, if they fit
@@ -1761,7 +1235,7 @@ __global__ __launch_bounds__(NTB) void level_sorted_kernel(
             s_best = 0;
         }
         __syncthreads();
-        SPHASE(0);
+        PHASE(0);
         // 1. the slice: bits of F and of the new set, LDS copy, blocks become active (roots
         // of themselves; a block, once active, stays active)
         for (int it = tid; it < nnew; it += NTB) {
@@ -1776,7 +1250,7 @@ __global__ __launch_bounds__(NTB) void level_sorted_kernel(
         }
         __syncthreads();
         auto newpx = [&](int it) -> uint32_t { return inl ? (uint32_t)lst[it] : slist[s0 + it]; };
-        SPHASE(1);
+        PHASE(1);
         // 2. new pixels unite their block with the adjacent blocks that hold a set 8-neighbour:
         // a pixel's 8 neighbours outside its own block lie in three blocks — horizontal
         // (2 pixels), vertical (2) and diagonal (1) — one lane per (pixel, block)
@@ -1801,7 +1275,7 @@ __global__ __launch_bounds__(NTB) void level_sorted_kernel(
                          &s_nhook);
         }
         __syncthreads();
-        SPHASE(2);
+        PHASE(2);
         // 3. roots hooked this level that held pixels hand their area, key and box to their
         // new root (roots activated this level hold none yet: key 0xFFFF)
         const int nhook = s_nhook;
@@ -1821,7 +1295,7 @@ __global__ __launch_bounds__(NTB) void level_sorted_kernel(
         }
         // (no barrier: step 4 only updates current roots, which step 3 never reads from,
         // and the updates commute)
-        SPHASE(3);
+        PHASE(3);
         // 4. window-area deltas (one lane per (pixel, window)), first-pixel keys, and the
         // box of each root widened by its new pixels
         for (int it = tid; it < nnew * 4; it += NTB) {
@@ -1852,7 +1326,7 @@ __global__ __launch_bounds__(NTB) void level_sorted_kernel(
             }
         }
         __syncthreads();
-        SPHASE(4);
+        PHASE(4);
         // 5. path compression after merges; the winner over the touched roots (each touched
         // block's path compressed on the way: no unites run in this step, and a non-root
         // re-pointed at its root keeps every find_root correct)
@@ -1880,7 +1354,7 @@ __global__ __launch_bounds__(NTB) void level_sorted_kernel(
         }
         for (int it = tid; it < nhook; it += NTB) cand(hlv[it] >> 16);
         if (tid == 0 && pwin != INACT) cand(pwin);
-        SPHASE(5);
+        PHASE(5);
         // block max: wave max, one LDS atomicMax per wave, one barrier
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
@@ -1907,7 +1381,7 @@ __global__ __launch_bounds__(NTB) void level_sorted_kernel(
         }
         const uint32_t fp = (uint32_t)best;   // the winner's first pixel
         const uint32_t wroot = find_root_pk(pk, ((fp / W) >> 1) * BW + ((fp % W) >> 1));
-        SPHASE(6);
+        PHASE(6);
         // 6. its box, off the root
         if (tid == 0) {
             const uint32_t xw = (xr[wroot >> 1] >> ((wroot & 1u) * 16)) & 0xFFFFu;
@@ -1920,7 +1394,7 @@ __global__ __launch_bounds__(NTB) void level_sorted_kernel(
         }
         pwin = wroot;
         __syncthreads();
-        SPHASE(7);
+        PHASE(7);
     }
     if (dbg && tid == 0) {
         uint64_t* d = dbg + (long)blockIdx.x * DBG_SLOTS;
@@ -1929,21 +1403,28 @@ __global__ __launch_bounds__(NTB) void level_sorted_kernel(
         d[9] = n_comp;
         d[10] = n_fallback;
     }
-#undef SPHASE
+#undef PHASE
 }
 }  // namespace
 
-static size_t inc_list_offset(int B, int H, int W) {
-    const size_t psi = ((size_t)B * H * W + 15) / 16 * 16;
-    return (psi + (size_t)B * (256 + 256 + 1) * sizeof(int32_t) + 255) / 256 * 256;
+// Workspace layout (tcam_bbox_ws_bytes):
+//   psi (B x H x W uint8), padded to 16 bytes
+//   | canon (B x 256 int32) | lev_list (B x 256 int32) | nlev (B int32), padded to 256 bytes
+//   | hooked-root lists of the sorted sweep (B * INC_MAX_CHUNKS x 112^2 uint32: one per
+//     workgroup; a block is hooked at most once)
+//   | psi-sorted pixel lists (B x H x W uint16), padded to 256 bytes
+//   | their level offsets, cgt (B x 257 int32)
+static size_t tables_offset(int B, int H, int W) {
+    return ((size_t)B * H * W + 15) / 16 * 16;
 }
 
-static size_t inc_hook_offset(int B, int H, int W) {
-    return inc_list_offset(B, H, W) + (size_t)B * INC_MAX_CHUNKS * IH * IW * sizeof(uint32_t);
+static size_t hook_list_offset(int B, int H, int W) {
+    return (tables_offset(B, H, W) + (size_t)B * (256 + 256 + 1) * sizeof(int32_t) + 255) / 256 *
+           256;
 }
 
 static size_t sorted_list_offset(int B, int H, int W) {
-    return inc_hook_offset(B, H, W) + (size_t)B * INC_MAX_CHUNKS * INB * sizeof(uint32_t);
+    return hook_list_offset(B, H, W) + (size_t)B * INC_MAX_CHUNKS * INB * sizeof(uint32_t);
 }
 
 static size_t sorted_cgt_offset(int B, int H, int W) {
@@ -1953,10 +1434,6 @@ static size_t sorted_cgt_offset(int B, int H, int W) {
 extern "C" void tcam_bbox_set_chunks(int n) { g_bbox_chunks = n; }
 
 extern "C" size_t tcam_bbox_ws_bytes(int B, int H, int W) {
-    // psi (uint8, 16-byte aligned) | canon (B x 256) | lev_list (B x 256) | nlev (B)
-    // | new-pixel lists of the incremental level sweep (B * INC_MAX_CHUNKS x 224^2 uint32)
-    // | hooked-root lists (B * INC_MAX_CHUNKS x 112^2 uint32)
-    // | psi-sorted pixel lists (B x H x W uint16) | their level offsets (B x 257 int32)
     return sorted_cgt_offset(B, H, W) + (size_t)B * 257 * sizeof(int32_t);
 }
 
@@ -1964,34 +1441,35 @@ extern "C" int tcam_bbox_levels(const uint8_t* cam_u8, int32_t* boxes, int32_t* 
                                 void* ws, int B, int H, int W, void* stream) {
     TCAM_REQUIRE(cam_u8 && boxes && vmax && ws && B > 0);
     TCAM_REQUIRE(H > 0 && W > 0 && H <= BIGH && W <= BIGW);
-    const bool big = H > MAXH || W > MAXW;
     hipStream_t st = as_stream(stream);
+    char* base = (char*)ws;
     uint8_t* psi = (uint8_t*)ws;
-    int32_t* canon = (int32_t*)((char*)ws + ((size_t)B * H * W + 15) / 16 * 16);
+    int32_t* canon = (int32_t*)(base + tables_offset(B, H, W));
     int32_t* lev_list = canon + (size_t)B * 256;
     int32_t* nlev = lev_list + (size_t)B * 256;
-    // level sweep: 0 = sorted list (frames <= 224^2), 1 = per-level CCL, 2 = incremental
-    const bool small = !big && H <= IH && W <= IW && !g_dbg;
-    const bool sorted = small && g_level_variant == 0;
-    uint16_t* slist = sorted ? reinterpret_cast<uint16_t*>((char*)ws + sorted_list_offset(B, H, W))
-                             : nullptr;
-    int32_t* cgt = reinterpret_cast<int32_t*>((char*)ws + sorted_cgt_offset(B, H, W));
-    if (big)
+    uint32_t* hooks = (uint32_t*)(base + hook_list_offset(B, H, W));
+    // the frame sizes that the kernels serve (the table in the header comment)
+    const bool upto224 = H <= IH && W <= IW, upto256 = H <= MAXH && W <= MAXW;
+    // the sorted sweep takes the level stage up to 224^2, unless level_kernel is asked for
+    // as the cross-check or for its phase times (tcam_bbox_set_debug)
+    const bool sorted = upto224 && g_level_variant == 0 && !g_dbg;
+    // it alone reads the psi-sorted pixel list, which the fill writes when given one
+    uint16_t* slist = sorted ? (uint16_t*)(base + sorted_list_offset(B, H, W)) : nullptr;
+    int32_t* cgt = sorted ? (int32_t*)(base + sorted_cgt_offset(B, H, W)) : nullptr;
+
+    // ---- fill
+    if (!upto256)                  // up to 320^2: psi alone in LDS
         fill_kernel<BIGH, BIGP, false><<<B, NTB, 0, st>>>(cam_u8, psi, vmax, canon, lev_list,
-                                                          nlev, H, W, g_dbg, nullptr, nullptr);
-    else if (g_fill_variant == 1)
+                                                          nlev, H, W, g_dbg, slist, cgt);
+    else if (g_fill_variant == 1)  // the cross-check, up to 256^2
         fill_kernel<MAXH, MAXP, true><<<B, NTB, 0, st>>>(cam_u8, psi, vmax, canon, lev_list,
                                                          nlev, H, W, g_dbg, slist, cgt);
-    else if (g_fill_variant == 0)
+    else                           // up to 256^2
         fill_scan_kernel<<<B, NTS, 0, st>>>(cam_u8, psi, vmax, canon, lev_list, nlev, H, W, slist,
                                             cgt, g_dbg, g_fill_waves, g_fill_maxit);
-    else if (H <= 224 && W <= 224)
-        fill_reg_kernel<56><<<B, NTF, 0, st>>>(cam_u8, psi, vmax, canon, lev_list, nlev, H, W,
-                                               g_dbg, slist, cgt);
-    else
-        fill_reg_kernel<64><<<B, NTF, 0, st>>>(cam_u8, psi, vmax, canon, lev_list, nlev, H, W,
-                                               g_dbg, slist, cgt);
     TCAM_CHECK_LAUNCH();
+
+    // ---- level stage
     // debug layout: fill rows [0, B*16) x DBG_SLOTS, level rows follow
     // level ranges per frame: more ranges = shorter latency, more CU-time (each range
     // rebuilds its top level from scratch); TCAM_BBOX_INC_CHUNKS (1..4) for A/B runs
@@ -2010,22 +1488,15 @@ extern "C" int tcam_bbox_levels(const uint8_t* cam_u8, int32_t* boxes, int32_t* 
         const char* e = getenv("TCAM_BBOX_COMPRESS");
         return e ? atoi(e) : 0;
     }();
-    if (sorted)
-        level_sorted_kernel<<<B * nc, NTB, 0, st>>>(
-            slist, cgt, lev_list, nlev, boxes, H, W,
-            reinterpret_cast<uint32_t*>((char*)ws + inc_hook_offset(B, H, W)), g_inc_dbg, nc,
-            compress);
-    else if (small && g_level_variant == 2)
-        level_inc_kernel<<<B * nc, NTB, 0, st>>>(
-            psi, lev_list, nlev, boxes, H, W,
-            reinterpret_cast<uint32_t*>((char*)ws + inc_list_offset(B, H, W)),
-            reinterpret_cast<uint32_t*>((char*)ws + inc_hook_offset(B, H, W)), g_inc_dbg, nc);
-    else if (big)
-        level_kernel<BIGH, BIGW, 4><<<B * LEVEL_CHUNKS, NTB, 0, st>>>(
-            psi, vmax, lev_list, nlev, boxes, H, W, g_dbg ? g_dbg + 0 : nullptr);
-    else
-        level_kernel<MAXH, MAXW, 2><<<B * LEVEL_CHUNKS, NTB, 0, st>>>(
-            psi, vmax, lev_list, nlev, boxes, H, W, g_dbg ? g_dbg + 0 : nullptr);
+    if (sorted)        // up to 224^2
+        level_sorted_kernel<<<B * nc, NTB, 0, st>>>(slist, cgt, lev_list, nlev, boxes, H, W, hooks,
+                                                    g_inc_dbg, nc, compress);
+    else if (upto256)  // up to 256^2, and the cross-check below that
+        level_kernel<MAXH, MAXW, 2><<<B * LEVEL_CHUNKS, NTB, 0, st>>>(psi, vmax, lev_list, nlev,
+                                                                      boxes, H, W, g_dbg);
+    else               // up to 320^2
+        level_kernel<BIGH, BIGW, 4><<<B * LEVEL_CHUNKS, NTB, 0, st>>>(psi, vmax, lev_list, nlev,
+                                                                      boxes, H, W, g_dbg);
     TCAM_CHECK_LAUNCH();
     expand_kernel<<<cdiv((long)B * 256, 256), 256, 0, st>>>(canon, vmax, boxes, B);
     TCAM_CHECK_LAUNCH();
@@ -2041,23 +1512,24 @@ extern "C" int tcam_bbox_scan_line(const uint8_t* p, const uint8_t* u, uint8_t* 
     return TCAM_OK;
 }
 
-// Debug/profiling hook: when non-null, fill_kernel writes per-frame phase
-// times (s_memrealtime ticks, 100 MHz) to buf[b*16 + 0..4] (load, sweeps,
-// histogram, iterations, levels) and level_kernel accumulates per-phase
-// ticks to buf[(gridDim + wg)*16 + 0..6].  buf must hold
-// (B + 2*B*16) * 16 uint64.
+// Profiling hook of the sorted-list sweep: when non-null, workgroup wg of level_sorted_kernel
+// writes its per-phase ticks (s_memrealtime, 100 MHz) to buf[wg*16 + 0..7], the levels it
+// processed to slot 8, its compression passes to slot 9 and its full winner passes to slot 10.
+// buf must hold B * chunks * 16 uint64.
 extern "C" int tcam_bbox_set_inc_debug(uint64_t* buf) {
     g_inc_dbg = buf;
     return TCAM_OK;
 }
 
-// where a level sweep applies (frames <= 224^2): 0 = the sorted-list sweep (default),
-// 1 = level_kernel (per-level CCL, the reference check), 2 = the incremental sweep
+// 0 = the sorted-list sweep where it applies (frames <= 224^2, default), 1 = level_kernel
+// (per-level CCL, the reference check) always
 extern "C" int tcam_bbox_level_variant(int v) {
+    TCAM_REQUIRE(v == 0 || v == 1);
     g_level_variant = v;
     return TCAM_OK;
 }
 
+// 0 = the clamp-scan fill (default), 1 = fill_kernel (LDS sweeps, the reference check)
 extern "C" int tcam_bbox_fill_variant(int v) {
     if (v >= 1000) {  // (debug) 1000 + k: at most k row + column passes (0: no limit)
         g_fill_maxit = v == 1000 ? 1 << 30 : v - 1000;
@@ -2067,10 +1539,17 @@ extern "C" int tcam_bbox_fill_variant(int v) {
         g_fill_waves = v - 100;
         return TCAM_OK;
     }
+    TCAM_REQUIRE(v == 0 || v == 1);
     g_fill_variant = v;
     return TCAM_OK;
 }
 
+// Debug/profiling hook: when non-null, the fill kernel writes per-frame phase
+// times (s_memrealtime ticks, 100 MHz) to buf[b*16 + 0..4] (load, sweeps,
+// histogram, iterations, and the distinct levels from fill_kernel or the
+// sorted-list ticks from fill_scan_kernel) and level_kernel, which then takes
+// the level stage at every frame size, accumulates per-phase ticks to
+// buf[(gridDim + wg)*16 + 0..6].  buf must hold 2 * B * 16 * 16 uint64.
 extern "C" int tcam_bbox_set_debug(uint64_t* buf) {
     g_dbg = buf;
     return TCAM_OK;

@@ -193,23 +193,22 @@ def test_bbox_levels_bit_exact_vs_oracle(cuda, kind, H, W):
         np.testing.assert_array_equal(boxes[b][levels], ref)
 
 
-@pytest.mark.parametrize("variant", [0, 2])
 @pytest.mark.parametrize("kind,H,W", [("smooth", 224, 224), ("noise", 224, 224),
                                       ("binary", 64, 80), ("blobs", 97, 131),
                                       ("smooth", 5, 3), ("blobs", 224, 200), ("zeros", 8, 8),
                                       ("binary", 224, 224), ("blobs", 1, 224), ("noise", 224, 1),
                                       ("rings", 224, 224), ("rings", 61, 97), ("rings", 224, 3)])
-def test_bbox_incremental_levels_match_per_level_ccl(cuda, kind, H, W, variant):
-    """The level sweeps for frames <= 224^2 — the sorted-list sweep (0, default) and the
-    incremental sweep (2) — give exactly the boxes of the per-level CCL kernel on every level
-    (which the test above pins to the oracle)."""
+def test_bbox_sorted_sweep_matches_per_level_ccl(cuda, kind, H, W):
+    """The sorted-list sweep, the level stage of frames <= 224^2, gives exactly the boxes of
+    the per-level CCL kernel (level variant 1) on every level, which the test above pins to
+    the oracle."""
     from tcam_wsol_video_amd import _lib
     lib = _lib.load()
     u8 = torch.from_numpy(_cams(kind, 6, H, W, seed=H + W + 7)).to(cuda)
     try:
-        lib.tcam_bbox_level_variant(1)
+        assert lib.tcam_bbox_level_variant(1) == 0
         b1, v1 = ops.bbox_levels(u8)
-        lib.tcam_bbox_level_variant(variant)
+        assert lib.tcam_bbox_level_variant(0) == 0
         b0, v0 = ops.bbox_levels(u8)
     finally:
         lib.tcam_bbox_level_variant(0)
@@ -222,15 +221,15 @@ def test_bbox_incremental_levels_match_per_level_ccl(cuda, kind, H, W, variant):
                                       ("blobs", 97, 131), ("smooth", 5, 3), ("binary", 256, 250),
                                       ("noise", 1, 200), ("blobs", 224, 1)])
 def test_bbox_fill_variants_agree(cuda, kind, H, W):
-    """The clamp-scan fill (default), the LDS-sweep fill and the register-line fill give the
-    same psi, hence the same boxes on every level."""
+    """The clamp-scan fill (default) and the LDS-sweep fill give the same psi, hence the same
+    boxes on every level."""
     from tcam_wsol_video_amd import _lib
     lib = _lib.load()
     u8 = torch.from_numpy(_cams(kind, 5, H, W, seed=H * 3 + W)).to(cuda)
     outs = []
     try:
-        for v in (0, 1, 2):
-            lib.tcam_bbox_fill_variant(v)
+        for v in (0, 1):
+            assert lib.tcam_bbox_fill_variant(v) == 0
             outs.append(ops.bbox_levels(u8))
     finally:
         lib.tcam_bbox_fill_variant(0)
@@ -241,17 +240,22 @@ def test_bbox_fill_variants_agree(cuda, kind, H, W):
         assert torch.equal(bx * valid, b0 * valid)
 
 
-def test_bbox_incremental_winner_key_drop(cuda):
-    """The incremental sweep takes the winner over the roots touched at a level; when the
-    previous winner's first-pixel key drops with no area gain (a new pixel joins it
-    diagonally, before its first pixel in raster order) an untouched root of equal area
-    takes over, which only the full fallback pass sees."""
-    from oracle import bbox_ref as BR
-    from tcam_wsol_video_amd import _lib
+def _key_drop_cams():
     u8 = np.zeros((2, 8, 12), np.uint8)
     u8[:, 2:4, 2:4] = 200    # A: first pixel 26, wins the tie at levels 150..199
     u8[:, 1:3, 8:10] = 200   # B: first pixel 20, same area
     u8[0, 1, 1] = 150        # joins A at level 149 with no area: A's key 26 -> 13
+    return u8
+
+
+def test_bbox_incremental_winner_key_drop(cuda):
+    """The sorted-list sweep carries its union-find from level to level and takes the winner
+    over the roots touched at a level; when the previous winner's first-pixel key drops with
+    no area gain (a new pixel joins it diagonally, before its first pixel in raster order) an
+    untouched root of equal area takes over, which only the full fallback pass sees."""
+    from oracle import bbox_ref as BR
+    from tcam_wsol_video_amd import _lib
+    u8 = _key_drop_cams()
     lib = _lib.load()
     t = torch.from_numpy(u8).to(cuda)
     b0, v0 = ops.bbox_levels(t)
@@ -267,6 +271,66 @@ def test_bbox_incremental_winner_key_drop(cuda):
         np.testing.assert_array_equal(b0[b][levels], b1.cpu().numpy()[b][levels])
     assert tuple(b0[0][149]) == (8, 1, 10, 3)   # B (x0, y0, x0 + w, y0 + h)
     assert tuple(b0[0][150]) == (2, 2, 4, 4)    # A
+
+
+def test_bbox_retired_variants_are_refused(cuda):
+    """The fill and level switches take 0 (production) and 1 (cross-check) only: the retired
+    variant 2 and a negative value return an error and leave the settings as they were."""
+    from tcam_wsol_video_amd import _lib
+    lib = _lib.load()
+    t = torch.from_numpy(_key_drop_cams()).to(cuda)
+    b0, v0 = ops.bbox_levels(t)
+    try:
+        assert lib.tcam_bbox_fill_variant(2) != 0
+        assert lib.tcam_bbox_fill_variant(-1) != 0
+        assert lib.tcam_bbox_level_variant(2) != 0
+        assert lib.tcam_bbox_level_variant(-1) != 0
+        b1, v1 = ops.bbox_levels(t)
+    finally:
+        lib.tcam_bbox_fill_variant(0)
+        lib.tcam_bbox_level_variant(0)
+    assert torch.equal(v1, v0)
+    # (rows >= vmax are never written: uninitialised memory of each call's own tensor)
+    valid = (torch.arange(256, device=cuda)[None, :] < v0[:, None])[..., None]
+    assert torch.equal(b1 * valid, b0 * valid)
+
+
+@pytest.mark.parametrize("kind,B,H,W,chunks", [("noise", 2, 224, 224, 4),   # most hooks per
+                                               # level, on the four ranges the lists are sized for
+                                               ("smooth", 2, 5, 3, 0),
+                                               ("binary", 1, 256, 250, 0),   # level_kernel path
+                                               ("binary", 1, 261, 320, 0)])  # large path
+def test_bbox_workspace_guards_intact(cuda, kind, B, H, W, chunks):
+    """tcam_bbox_levels on a workspace of exactly tcam_bbox_ws_bytes, between two guard
+    regions: the guards stay intact and the boxes are those of ops.bbox_levels; and the size
+    is the sum of the regions the kernels use."""
+    from tcam_wsol_video_amd import _lib
+    lib = _lib.load()
+    G = 4096   # (keeps the workspace's 256-byte alignment)
+    u8 = torch.from_numpy(_cams(kind, B, H, W, seed=H * 5 + W)).to(cuda)
+    b_ref, v_ref = ops.bbox_levels(u8)
+    n = int(lib.tcam_bbox_ws_bytes(B, H, W))
+    buf = torch.full((n + 2 * G,), 0xA5, device=cuda, dtype=torch.uint8)
+    boxes = torch.empty((B, 256, 4), device=cuda, dtype=torch.int32)
+    vmax = torch.empty((B,), device=cuda, dtype=torch.int32)
+    lib.tcam_bbox_set_chunks(chunks)
+    try:
+        rc = lib.tcam_bbox_levels(u8.data_ptr(), boxes.data_ptr(), vmax.data_ptr(),
+                                  buf.data_ptr() + G, B, H, W,
+                                  torch.cuda.current_stream().cuda_stream)
+    finally:
+        lib.tcam_bbox_set_chunks(0)
+    assert rc == 0
+    torch.cuda.synchronize()
+    assert bool((buf[:G] == 0xA5).all()) and bool((buf[G + n:] == 0xA5).all())
+    assert torch.equal(vmax, v_ref)
+    valid = (torch.arange(256, device=cuda)[None, :] < v_ref[:, None])[..., None]
+    assert torch.equal(boxes * valid, b_ref * valid)
+    # per 224 x 224 frame: psi 50176 + level tables 2052 + hooked-root lists 4 x 112^2 x 4 =
+    # 200704 + sorted pixel list 100352 + its offsets 1028 = 354312 bytes, plus under 1 KB of
+    # alignment per call
+    for nb in (1, 32):
+        assert lib.tcam_bbox_ws_bytes(nb, 224, 224) <= nb * 354312 + 1024
 
 
 def test_box_accumulate_matches_reference_evaluator(cuda):
