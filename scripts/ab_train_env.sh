@@ -1,6 +1,6 @@
 # A/B of environment settings on the training step (scripts/bench_train.py), interleaved,
 # with a heartbeat -> gpurun_out/ab_train_env.txt
-#   VARIANTS="base=X=0 pipe=TCAM_WGRAD_PIPE=1" ARGS="--amp" bash scripts/ab_train_env.sh
+#   VARIANTS="base=X=0 inline=TCAM_WGRAD_SIDE=0" ARGS="--amp" bash scripts/ab_train_env.sh
 ROUNDS=${ROUNDS:-2}
 mkdir -p gpurun_out
 ( while true; do date >> gpurun_out/heartbeat.txt; sleep 20; done ) &

@@ -35,18 +35,15 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
-from ._lib import check, tcam_conv_src, tcam_pack_item
+from . import _lib, ops, train_ops
+from ._lib import check, tcam_pack_item
 from .flat_sgd import FlatSGD, _stream
 from .models import RESNET50, STDClassifier
 from .ops import ConvSrc
+from .train_ops import Grad, _p, pack_weight
 
 # STDClassifier's eval plans fold encoder weights / BN statistics
 ENCODER_PLANS = ("enc_x6", "enc_f16x3", "enc_amp", "enc")
-
-
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
 
 
 class _EConv:
@@ -79,10 +76,10 @@ class _Block:
 
 class Stage1Trainer(FlatSGD):
     """What the stage-1 trainers of every encoder share: the constructor arguments, the
-    precision and its formats, the weight packing, the WGAP head, ClLoss and the step.  A
-    subclass names its encoder (``ENCODER``), splits the parameters into the reference's two
-    SGD groups (:meth:`param_split`), builds its conv stack (:meth:`_build`) and has
-    ``repack``, ``forward`` and ``backward``."""
+    precision and its formats, the WGAP head, ClLoss and the step (the layer ops are
+    :mod:`~.train_ops`).  A subclass names its encoder (``ENCODER``), splits the parameters
+    into the reference's two SGD groups (:meth:`param_split`), builds its conv stack
+    (:meth:`_build`) and has ``repack``, ``forward`` and ``backward``."""
 
     PLANS = ENCODER_PLANS
     ENCODER = ""
@@ -137,38 +134,6 @@ class Stage1Trainer(FlatSGD):
 
     def close(self) -> None:
         """(the trainer keeps nothing for the next step)"""
-
-    def _pack(self, w: torch.Tensor, mode: int, sel: int = 0, cin_pad: int = 0,
-              kdiv: Optional[torch.Tensor] = None, out=None):
-        """The MFMA operand of conv weight ``w`` (Cout, Cin, KH, KW): mode 0 the forward's,
-        mode 1 the data gradient's (transposed, rotated, over the first ``sel`` input
-        channels, divided by ``kdiv`` = dy's per-channel scales on the f16x3 path).
-        Returns (wt, wscale or None)."""
-        cout, ctot, kh, kw = w.shape
-        if mode == 0:
-            K, M = kh * kw * max(ctot, cin_pad), cout
-        else:
-            K, M = kh * kw * cout, sel
-        kp, mp = ops.conv_x6_weight_dims(K, M)
-        lib = _lib.load()
-        if self.amp:
-            wt = out[0] if out is not None and out[0] is not None and \
-                tuple(out[0].shape) == (kp // 32, 4, 1, mp, 8) else \
-                torch.empty((kp // 32, 4, 1, mp, 8), device=self.dev, dtype=torch.float16)
-            check(lib.tcam_pack_weight_f16(w.data_ptr(), wt.data_ptr(), mode, cout, ctot, kh, kw,
-                                           0, sel if mode else 0, cin_pad, _stream()),
-                  "tcam_pack_weight_f16")
-            return wt, None
-        if out is not None and out[0] is not None and \
-                tuple(out[0].shape) == (kp // 32, 4, 2, mp, 8):
-            wt, sc = out
-        else:
-            wt = torch.empty((kp // 32, 4, 2, mp, 8), device=self.dev, dtype=torch.float16)
-            sc = torch.empty(mp, device=self.dev, dtype=torch.float32)
-        check(lib.tcam_pack_weight_f16x3(w.data_ptr(), wt.data_ptr(), sc.data_ptr(), mode, cout,
-                                         ctot, kh, kw, 0, sel if mode else 0, cin_pad,
-                                         _p(kdiv), _stream()), "tcam_pack_weight_f16x3")
-        return wt, sc
 
     def _images_s3(self, images: torch.Tensor) -> torch.Tensor:
         """The batch as the first conv's input (8 stored channels), the operands repacked
@@ -282,9 +247,6 @@ class ClassifierTrainer(Stage1Trainer):
         self.bns = [m for m in model.modules() if isinstance(m, nn.BatchNorm2d)]
         self._ws: Dict[str, torch.Tensor] = {}
         self.wgrad_side = os.environ.get("TCAM_WGRAD_SIDE", "1") != "0"
-        # the fused BN-ReLU backward with a bound-based MFMA scale (TCAM_FUSED_BN_BWD=0: the
-        # three-pass path: backward + channel maxima, scale, re-split)
-        self.fused_bn_bwd = os.environ.get("TCAM_FUSED_BN_BWD", "1") != "0"
         # the stem's weight gradient as im2col + the 1x1 MFMA GEMM (0: the fp32-MFMA general path)
         self.stem_im2col = os.environ.get("TCAM_STEM_IM2COL", "1") != "0"
         # the repack as one batched launch (two on f16x3) once the operand buffers exist
@@ -329,10 +291,11 @@ class ClassifierTrainer(Stage1Trainer):
         if not self.batched_pack or any(c.wt is None for c in convs) or \
                 any(c.dwt is None for c in dconvs):
             for c in convs:
-                c.wt, c.wsc = self._pack(c.conv.weight.data, 0, cin_pad=c.cin_pad,
-                                         out=(c.wt, c.wsc))
+                c.wt, c.wsc = pack_weight(c.conv.weight.data, self.fmt, 0, cin_pad=c.cin_pad,
+                                          out=(c.wt, c.wsc))
             for c in dconvs:
-                c.dwt, _ = self._pack(c.conv.weight.data, 1, sel=c.cin, out=(c.dwt, None))
+                c.dwt, _ = pack_weight(c.conv.weight.data, self.fmt, 1, sel=c.cin,
+                                       out=(c.dwt, None))
             return
         n = len(convs) + len(dconvs)
         if self._pack_items is None or len(self._pack_items) != n:
@@ -360,77 +323,21 @@ class ClassifierTrainer(Stage1Trainer):
                              wscale=c.wsc)
 
     def _bn_stats(self, c: _EConv, y: torch.Tensor):
-        lib = _lib.load()
-        B, H, W, Cc = ops.s3_dims(y)
-        P = B * H * W
-        ws = self._workspace("bn", int(lib.tcam_bn_ws_bytes(P, Cc)))
-        mean = torch.empty(Cc, device=self.dev)
-        invstd = torch.empty(Cc, device=self.dev)
-        bn = c.bn
-        check(getattr(lib, f"tcam_bn_stats_{self.lay}")(
-            y.data_ptr(), P, Cc, bn.eps, bn.momentum, mean.data_ptr(), invstd.data_ptr(),
-            bn.running_mean.data_ptr(), bn.running_var.data_ptr(), ws.data_ptr(), _stream()),
-            f"tcam_bn_stats_{self.lay}")
-        return mean, invstd
+        return train_ops.bn_stats(y, c.bn, self.lay,
+                                  self._workspace("bn", train_ops.bn_ws_bytes(y)))
 
     def _bn_relu(self, c: _EConv, y: torch.Tensor):
-        lib = _lib.load()
         mean, invstd = self._bn_stats(c, y)
-        B, H, W, Cc = ops.s3_dims(y)
-        out = torch.empty_like(y)
-        check(getattr(lib, f"tcam_bn_relu_{self.lay}")(
-            y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), c.bn.weight.data_ptr(),
-            c.bn.bias.data_ptr(), out.data_ptr(), B * H * W, Cc, _stream()),
-            f"tcam_bn_relu_{self.lay}")
-        return out, mean, invstd
+        return train_ops.bn_relu(y, mean, invstd, c.bn, self.lay), mean, invstd
 
     def _bn_bwd(self, c: _EConv, dout, out, y, mean, invstd, scaled: bool = True,
-                masky: bool = False, need_s3: bool = False):
-        """dy of a BatchNorm whose output went through the ReLU that produced ``out``
-        (the mask): the f16x3 step returns (dy S3 or None, dy2, scale) — dy2 its
-        per-channel scaled S2 copy for the MFMA, from the fused backward (``masky``: a
-        BN-ReLU, the mask recomputed from y; ``need_s3``: dy itself too) — or (dy, None,
-        None) with ``scaled`` False; AMP returns (dy S1, None, None)."""
-        lib = _lib.load()
-        B, H, W, Cc = ops.s3_dims(y)
-        P = B * H * W
-        gw, gb = self.g(c.bn.weight), self.g(c.bn.bias)
-        if scaled and not self.amp and self.fused_bn_bwd:
-            ws = self._workspace("bn", int(lib.tcam_bn_bwd_scaled_ws_bytes(P, Cc)))
-            dy = ops.lay_empty("s3", B, H, W, Cc, self.dev) if need_s3 else None
-            dy2 = ops.lay_empty("s2", B, H, W, Cc, self.dev)
-            scale = torch.empty(Cc, device=self.dev, dtype=torch.float32)
-            check(lib.tcam_bn_relu_bwd_scaled_s3s2(
-                dout.data_ptr(), None if masky else out.data_ptr(), y.data_ptr(),
-                mean.data_ptr(), invstd.data_ptr(), c.bn.weight.data_ptr(),
-                c.bn.bias.data_ptr(), _p(dy), dy2.data_ptr(), scale.data_ptr(), gw.data_ptr(),
-                gb.data_ptr(), P, Cc, ws.data_ptr(), _stream()), "tcam_bn_relu_bwd_scaled_s3s2")
-            return dy, dy2, scale
-        ws = self._workspace("bn", int(lib.tcam_bn_ws_bytes(P, Cc)))
-        dy = ops.lay_empty(self.glay, B, H, W, Cc, self.dev)
-        if self.amp and self.fused_bn_bwd:
-            check(lib.tcam_bn_relu_bwd_fused_s1(
-                dout.data_ptr(), None if masky else out.data_ptr(), y.data_ptr(),
-                mean.data_ptr(), invstd.data_ptr(), c.bn.weight.data_ptr(),
-                c.bn.bias.data_ptr(), dy.data_ptr(), gw.data_ptr(), gb.data_ptr(), P, Cc,
-                ws.data_ptr(), _stream()), "tcam_bn_relu_bwd_fused_s1")
-            return dy, None, None
-        if self.amp:
-            check(lib.tcam_bn_relu_bwd_s1(dout.data_ptr(), out.data_ptr(), y.data_ptr(),
-                                          mean.data_ptr(), invstd.data_ptr(),
-                                          c.bn.weight.data_ptr(), dy.data_ptr(), gw.data_ptr(),
-                                          gb.data_ptr(), P, Cc, ws.data_ptr(), _stream()),
-                  "tcam_bn_relu_bwd_s1")
-            return dy, None, None
-        amax = torch.empty(Cc, device=self.dev, dtype=torch.int32) if scaled else None
-        check(lib.tcam_bn_relu_bwd_s3s2(dout.data_ptr(), out.data_ptr(), y.data_ptr(),
-                                        mean.data_ptr(), invstd.data_ptr(),
-                                        c.bn.weight.data_ptr(), dy.data_ptr(), gw.data_ptr(),
-                                        gb.data_ptr(), P, Cc, ws.data_ptr(), _p(amax), _stream()),
-              "tcam_bn_relu_bwd_s3s2")
-        if not scaled:
-            return dy, None, None
-        return (dy,) + self._dy_scaled(dy, amax)
+                masky: bool = False) -> Grad:
+        """The gradient of a BatchNorm whose output went through the ReLU that produced
+        ``out`` (the mask; ``masky``: a BN-ReLU, the mask recomputed from y).  f16x3: dy's
+        per-channel scaled S2 copy for the MFMA, or with ``scaled`` False the S3 dy alone."""
+        ws = self._workspace("bn", train_ops.bn_ws_bytes(y, scaled and not self.amp))
+        return train_ops.bn_relu_bwd(dout, out, y, mean, invstd, c.bn, self.g(c.bn.weight),
+                                     self.g(c.bn.bias), self.fmt, ws, scaled=scaled, masky=masky)
 
     def _dgrad(self, srcs, w: torch.Tensor, kdiv: Optional[torch.Tensor], sel: int, H: int,
                W: int, k: int, pad: int, c: Optional[_EConv] = None) -> torch.Tensor:
@@ -440,7 +347,7 @@ class ClassifierTrainer(Stage1Trainer):
         repack already packed (``c.dwt``), if it did."""
         if self.amp and c is not None and c.dwt is not None and self.batched_pack:
             return ops.conv2d_x6(srcs, c.dwt, self._zeros(sel), sel, H, W, k, k - 1 - pad, False)
-        wt, sc = self._pack(w, 1, sel=sel, kdiv=kdiv)
+        wt, sc = pack_weight(w, self.fmt, 1, sel=sel, kdiv=kdiv)
         if self.amp:
             return ops.conv2d_x6(srcs, wt, self._zeros(sel), sel, H, W, k, k - 1 - pad, False)
         return ops.conv2d_f16x3_s3out(srcs, wt, sc, self._zeros(sel), sel, H, W, k, k - 1 - pad)
@@ -472,43 +379,14 @@ class ClassifierTrainer(Stage1Trainer):
                                             ws.data_ptr(), ws.numel(), _stream()),
                   "tcam_wgrad11_s2_f16x3")
 
-    def _srcs(self, x: torch.Tensor, stride: int):
-        _, H, W, Cc = ops.s3_dims(x)
-        arr = (tcam_conv_src * 1)()
-        arr[0] = tcam_conv_src(x.data_ptr(), Cc, H, W, stride, 0)
-        return arr
-
-    def _wgrad_conv(self, x: torch.Tensor, c: _EConv, dy: torch.Tensor,
-                    dy2: Optional[torch.Tensor], dsc: Optional[torch.Tensor],
-                    dw: torch.Tensor, cout_store: Optional[int] = None,
+    def _wgrad_conv(self, x: torch.Tensor, c: _EConv, g: Grad, dw: torch.Tensor,
                     stride: Optional[int] = None) -> None:
-        """KxK weight gradient of conv ``c`` on input ``x``: the 3x3 / stride-1 fast path
-        (f16x3 on dy2 / dsc, or AMP's fp16 product) or the fp32-MFMA general path (dy).
-        ``stride`` overrides the conv's (1 with dy zero-inserted onto the input grid)."""
-        lib = _lib.load()
-        B, Ho, Wo, Cd = ops.s3_dims(dy if dy is not None else dy2)
-        stride = c.stride if stride is None else stride
-        arr = self._srcs(x, stride)
-        fast = c.k == 3 and stride == 1 and c.pad == 1
-        if self.amp:
-            nb = int(lib.tcam_conv_wgrad_ws_bytes(arr, 1, B, Cd, Ho, Wo, c.k, c.k))
-            ws = self._workspace("wg", nb)
-            check(lib.tcam_conv_wgrad_s1(arr, 1, B, dy.data_ptr(), Cd, Ho, Wo, c.k, c.k, c.pad,
-                                         c.pad, cout_store or Cd, dw.data_ptr(), ws.data_ptr(),
-                                         ws.numel(), _stream()), "tcam_conv_wgrad_s1")
-        elif fast:
-            nb = int(lib.tcam_conv_wgrad_ws_bytes(arr, 1, B, Cd, Ho, Wo, 3, 3))
-            ws = self._workspace("wg", nb)
-            check(lib.tcam_conv_wgrad_s2_f16x3(arr, 1, B, dy2.data_ptr(), dsc.data_ptr(), Cd, Ho,
-                                               Wo, 3, 3, 1, 1, cout_store or Cd, dw.data_ptr(),
-                                               ws.data_ptr(), ws.numel(), _stream()),
-                  "tcam_conv_wgrad_s2_f16x3")
-        else:
-            nb = int(lib.tcam_conv_wgrad_generic_ws_bytes(arr, 1, B, Cd, Ho, Wo, c.k, c.k))
-            ws = self._workspace("wg", nb)
-            check(lib.tcam_conv_wgrad_s3s2(arr, 1, B, dy.data_ptr(), Cd, Ho, Wo, c.k, c.k, c.pad,
-                                           c.pad, cout_store or Cd, dw.data_ptr(), ws.data_ptr(),
-                                           ws.numel(), _stream()), "tcam_conv_wgrad_s3s2")
+        """KxK weight gradient of conv ``c`` on input ``x`` (train_ops.conv_wgrad: the 3x3 /
+        stride-1 MFMA path or the fp32-MFMA general one).  ``stride`` overrides the conv's (1
+        with dy zero-inserted onto the input grid)."""
+        arr = train_ops.conv_srcs([ConvSrc(x, c.stride if stride is None else stride)])
+        ws = self._workspace("wg", train_ops.conv_wgrad_ws_bytes(arr, g, self.fmt, c.k, c.pad))
+        train_ops.conv_wgrad(arr, g, dw, ws, self.fmt, c.k, c.pad)
 
     # ------------------------------------------------------------ forward
     def forward(self, images: torch.Tensor):
@@ -586,23 +464,22 @@ class ClassifierTrainer(Stage1Trainer):
         s0, gw, x0 = self.stem, self.g(self.stem.conv.weight), st["x0"]
         if not self.stem_im2col:
             # the fp32-MFMA general path on the exact S3 dy (TCAM_STEM_IM2COL=0)
-            dy0, _, _ = self._bn_bwd(s0, da0, a0, y0, m0, i0, scaled=False)
+            g0 = self._bn_bwd(s0, da0, a0, y0, m0, i0, scaled=False)
             if self._stem_dw is None:
                 self._stem_dw = torch.empty((s0.cout, 8, s0.k, s0.k), device=self.dev,
                                             dtype=torch.float32)
             tmp = self._stem_dw
 
             def stem_wgrad():
-                self._wgrad_conv(x0, s0, dy0, None, None, tmp)
+                self._wgrad_conv(x0, s0, g0, tmp)
                 gw.copy_(tmp[:, :s0.cin])
-            self._side(stem_wgrad, x0, dy0, tmp)
+            self._side(stem_wgrad, x0, g0.dy, tmp)
             return
         # the 7x7/2 stem's weight gradient as a 1x1 one: every output pixel's 7x7 patch of the
         # 8-channel (3 real) image as 49 groups (tcam_im2col), then wgrad11's GEMM over pixels
         # (dW (64, 49 x 8) on the fp16 MFMA, f16x3 or AMP) — the general fp32-MFMA path took
         # ~2.2 ms at the end of the backward, with nothing left to overlap it
-        dy0, dy0s, sc0 = self._bn_bwd(s0, da0, a0, y0, m0, i0, masky=True)
-        op0 = dy0 if self.amp else dy0s
+        _, op0, sc0 = self._bn_bwd(s0, da0, a0, y0, m0, i0, masky=True)
         _, Hx, Wx, Cx = ops.s3_dims(x0)
         _, Ho0, Wo0, Co = ops.s3_dims(op0)
         taps = s0.k * s0.k
@@ -628,39 +505,31 @@ class ClassifierTrainer(Stage1Trainer):
         B, Hin, Win, Cin = ops.s3_dims(x)
         _, Ho, Wo, _ = ops.s3_dims(out)
         # bn3 (+ the projection's BN): the mask is the block output's relu3
-        dy3, dy3s, sc3 = self._bn_bwd(b.c3, dout, out, s["y3"], s["m3"], s["i3"])
+        _, op3, sc3 = self._bn_bwd(b.c3, dout, out, s["y3"], s["m3"], s["i3"])
         a2, a1 = s["a2"], s["a1"]
         g3 = self.g(b.c3.conv.weight).view(b.c3.cout, b.c3.cin)
-        op3 = dy3 if self.amp else dy3s
         self._side(lambda: self._wgrad11(a2, 1, op3, sc3, g3), a2, op3, sc3)
         if b.ds is not None:
-            dyd, dyds, scd = self._bn_bwd(b.ds, dout, out, s["yd"], s["md"], s["idd"])
+            _, opd, scd = self._bn_bwd(b.ds, dout, out, s["yd"], s["md"], s["idd"])
             gd = self.g(b.ds.conv.weight).view(b.ds.cout, b.ds.cin)
-            opd = dyd if self.amp else dyds
             sdd = b.ds.stride
             self._side(lambda: self._wgrad11(x, sdd, opd, scd, gd), x, opd, scd)
         # conv3 data gradient -> bn2
         da2 = self._dgrad([ConvSrc(op3)], b.c3.conv.weight.data, sc3, b.c3.cin, Ho, Wo, 1, 0,
                           c=b.c3)
-        dy2, dy2s, sc2 = self._bn_bwd(b.c2, da2, a2, s["y2"], s["m2"], s["i2"], masky=True)
-        g2 = self.g(b.c2.conv.weight)
-        op2 = dy2 if self.amp else dy2s
+        gr2 = self._bn_bwd(b.c2, da2, a2, s["y2"], s["m2"], s["i2"], masky=True)
+        g2, op2, sc2 = self.g(b.c2.conv.weight), gr2.op, gr2.scale
         # stride 2: dy spread onto the input grid (dy_up[2o] = dy[o], zeros between) turns both
         # gradients of the conv into stride-1 3x3 ones — dW[k] = sum_q dy_up[q] x[q - 1 + k],
         # the fast MFMA weight gradient instead of the fp32-MFMA general path
         src2 = op2 if b.c2.stride == 1 else self._zero_up2(op2, Hin, Win)
-        if b.c2.stride == 1:
-            self._side(lambda: self._wgrad_conv(a1, b.c2, dy2, dy2s, sc2, g2), a1, dy2, dy2s, sc2)
-        else:
-            wdy, wdy2 = (src2, None) if self.amp else (None, src2)
-            self._side(lambda: self._wgrad_conv(a1, b.c2, wdy, wdy2, sc2, g2, stride=1),
-                       a1, src2, sc2)
+        self._side(lambda: self._wgrad_conv(a1, b.c2, Grad(None, src2, sc2), g2, stride=1),
+                   a1, src2, sc2)
         # conv2 data gradient -> bn1
         da1 = self._dgrad([ConvSrc(src2)], b.c2.conv.weight.data, sc2, b.c2.cin, Hin, Win, 3, 1,
                           c=b.c2)
-        dy1, dy1s, sc1 = self._bn_bwd(b.c1, da1, a1, s["y1"], s["m1"], s["i1"], masky=True)
+        _, op1, sc1 = self._bn_bwd(b.c1, da1, a1, s["y1"], s["m1"], s["i1"], masky=True)
         g1 = self.g(b.c1.conv.weight).view(b.c1.cout, b.c1.cin)
-        op1 = dy1 if self.amp else dy1s
         self._side(lambda: self._wgrad11(x, 1, op1, sc1, g1), x, op1, sc1)
         # d x: conv1's data gradient + the shortcut's
         if b.ds is None:

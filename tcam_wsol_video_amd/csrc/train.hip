@@ -222,21 +222,6 @@ __global__ __launch_bounds__(kB) void bn_bwd_partial_co_kernel(
     }
 }
 
-__global__ __launch_bounds__(kB) void bn_bwd_finalize_kernel(const double* __restrict__ part,
-                                                             int nchunks, int C,
-                                                             float* __restrict__ dgamma,
-                                                             float* __restrict__ dbeta,
-                                                             float* __restrict__ coef) {
-    const int c = blockIdx.x;
-    double s, q;
-    chunk_sum2(part, nchunks, C, c, s, q);
-    if (threadIdx.x != 0) return;
-    dbeta[c] = (float)s;
-    dgamma[c] = (float)q;
-    coef[2 * c] = (float)s;
-    coef[2 * c + 1] = (float)q;
-}
-
 template <class L, class LA = L>
 __global__ __launch_bounds__(kB) void bn_bwd_apply_kernel(
     const uint8_t* __restrict__ dout, const uint8_t* __restrict__ out,
@@ -1004,7 +989,7 @@ __device__ __forceinline__ V8 frag(v4i16 a, v4i16 b) {
     return __builtin_bit_cast(V8, v);
 }
 
-template <class F, int MSUB, bool PIPE = false>
+template <class F, int MSUB>
 __global__ __launch_bounds__(192) void wgrad33x6_kernel(W33Args a) {
     using C = W33X6<F, MSUB>;
     constexpr int NP = F::NP;
@@ -1083,12 +1068,8 @@ __global__ __launch_bounds__(192) void wgrad33x6_kernel(W33Args a) {
             }
         }
     };
-    // PIPE: software pipeline — patch q+1's loads are issued before patch q's MFMAs, so they
-    // land while the matrix pipe works (costs the registers of one patch in flight); else each
-    // patch's loads are issued at the top of its iteration
-    if (PIPE && q0 < q1) load_patch(q0);
     for (long q = q0; q < q1; ++q) {
-        if (!PIPE) load_patch(q);
+        load_patch(q);
         // (WgF3) x: S3 -> the S2 split, in registers
         uint4 xs[XIT][NP];
 #pragma unroll
@@ -1124,7 +1105,6 @@ __global__ __launch_bounds__(192) void wgrad33x6_kernel(W33Args a) {
             }
         }
         __syncthreads();
-        if (PIPE && q + 1 < q1) load_patch(q + 1);
         // 4 K-steps of 16 pixels: K-step ks covers patch row ks/2, columns 16(ks%2) ..
 #pragma unroll
         for (int ks = 0; ks < kPR * kPC / 16; ++ks) {
@@ -1297,79 +1277,45 @@ __global__ __launch_bounds__(kB) void wgrad_reduce_kernel(WgArgs a, int splits, 
 }
 
 // ------------------------------------------------------- weight pack
-// packed[kt][g][part][m][e] = part of Wsel[32 kt + 8 g + e][m], k = tap * Cin' + c'.
-// mode 0: Wsel[k][m] = W[m][c'][kh][kw] (W = (Cout, Ctot, KH, KW), Cin' = Ctot)
-// mode 1 (dgrad): outputs m over channels [c0, c0 + Cout') of W's inputs, inputs c' over
-//   W's outputs: Wsel[k][m] = W[c'][c0 + m][KH-1-kh][KW-1-kw]   (Cin' = W's Cout)
-__global__ __launch_bounds__(kB) void pack_kernel(const float* __restrict__ w,
-                                                  uint16_t* __restrict__ out, int mode,
-                                                  int CoutW, int CtotW, int KH, int KW, int c0,
-                                                  int Coutp, int Cinp, int Kpad, int Mpad,
-                                                  int h1) {
-    const long i = (long)blockIdx.x * kB + threadIdx.x;   // over Kpad * Mpad
-    if (i >= (long)Kpad * Mpad) return;
-    const int m = (int)(i % Mpad);
-    const int k = (int)(i / Mpad);
-    const int K = KH * KW * Cinp;
-    float v = 0.f;
-    if (k < K && m < Coutp) {
-        const int tap = k / Cinp, c = k - tap * Cinp;
-        const int kh = tap / KW, kw = tap - kh * KW;
-        if (mode == 0) {
-            if (c < CtotW) v = w[(((long)m * CtotW + c) * KH + kh) * KW + kw];
-        } else if (c < CoutW) {   // inputs c' >= CoutW: zero padding of a padded dy
-            v = w[(((long)c * CtotW + c0 + m) * KH + (KH - 1 - kh)) * KW + (KW - 1 - kw)];
-        }
-    }
-    const int kt = k / 32, g = (k / 8) & 3, e = k & 7;
-    if (h1) {   // FmtH1: (Kpad/32, 4, 1, Mpad, 8) fp16, the autocast cast of the weight
-        out[(((long)kt * 4 + g) * Mpad + m) * 8 + e] = (uint16_t)s2::hbits(v);
-        return;
-    }
-    const uint32_t hb = s3::bfbits(v);
-    const float r1 = v - __uint_as_float(hb << 16);
-    const uint32_t mb = s3::bfbits(r1);
-    const uint32_t lb = s3::bfbits(r1 - __uint_as_float(mb << 16));
-    const long base = ((((long)kt * 4 + g) * 3) * Mpad + m) * 8 + e;
-    out[base] = (uint16_t)hb;
-    out[base + (long)Mpad * 8] = (uint16_t)mb;
-    out[base + 2l * Mpad * 8] = (uint16_t)lb;
-}
+// One pack item: the PyTorch weight w (CoutW, CtotW, KH, KW) -> the MFMA operand of the conv
+// selected by (mode, c0, Coutp, Cinp), K = KH KW Cinp rows k = tap * Cinp + c', Coutp columns:
+// mode 0: Wsel[k][m] = W[m][c'][kh][kw]                       (Coutp = CoutW, Cinp >= CtotW)
+// mode 1 (dgrad): outputs m over channels [c0, c0 + Coutp) of W's inputs, inputs c' over
+//   W's outputs: Wsel[k][m] = W[c'][c0 + m][KH-1-kh][KW-1-kw]  (Cinp >= CoutW)
+// Rows c' beyond the weight's channels (the stem's 8-channel image, a padded dy), rows up to
+// Kpad and columns up to Mpad are zero.  kdiv (f16x3, or null): a power of two per input
+// channel c' that the weights are divided by (mode 1: dy's scales, which then divide out of
+// the data gradient exactly).
+struct PackDesc {
+    const float* w;
+    uint16_t* out;
+    float* wscale;
+    const float* kdiv;
+    int mode, CoutW, CtotW, KH, KW, c0, Coutp, Cinp, Kpad, Mpad;
+    int sb0, pb0;   // batched: the item's first block in the scale / pack launch
+};
 
-// The split f16x3 operand of a trainable conv (conv_x6.hip FmtF16, as ops.pack_conv_weight_f16
-// on the host): v = Wsel[k][m] / kdiv[c'] (kdiv: a power of two per input channel c' of the
-// selected conv, or none) over a per-column power-of-two scale s_m with max_k |v| / s_m in
-// [2^14, 2^15); parts h = rne_f16(v / s_m), l = rne_f16(v / s_m - h), layout
-// (Kpad/32, 4, 2, Mpad, 8).  Mode 1 with kdiv = dy's channel scales is the data-gradient
-// operand of the f16x3 step: the scales that put dy into fp16's range divide out exactly.
-__device__ __forceinline__ float pack_sel(const float* __restrict__ w, int mode, int CoutW,
-                                          int CtotW, int KH, int KW, int c0, int Coutp,
-                                          int Cinp, const float* __restrict__ kdiv, int k,
-                                          int m) {
-    const int K = KH * KW * Cinp;
-    if (k >= K || m >= Coutp) return 0.f;
-    const int tap = k / Cinp, c = k - tap * Cinp;
-    const int kh = tap / KW, kw = tap - kh * KW;
+__device__ __forceinline__ float pack_sel(const PackDesc& d, int k, int m) {
+    const int K = d.KH * d.KW * d.Cinp;
+    if (k >= K || m >= d.Coutp) return 0.f;
+    const int tap = k / d.Cinp, c = k - tap * d.Cinp;
+    const int kh = tap / d.KW, kw = tap - kh * d.KW;
     float v = 0.f;
-    if (mode == 0) {
-        if (c < CtotW) v = w[(((long)m * CtotW + c) * KH + kh) * KW + kw];
-    } else if (c < CoutW) {
-        v = w[(((long)c * CtotW + c0 + m) * KH + (KH - 1 - kh)) * KW + (KW - 1 - kw)];
+    if (d.mode == 0) {
+        if (c < d.CtotW) v = d.w[(((long)m * d.CtotW + c) * d.KH + kh) * d.KW + kw];
+    } else if (c < d.CoutW) {
+        v = d.w[(((long)c * d.CtotW + d.c0 + m) * d.KH + (d.KH - 1 - kh)) * d.KW +
+                (d.KW - 1 - kw)];
     }
-    if (kdiv && c < (mode == 0 ? CtotW : CoutW)) v = v / kdiv[c];   // a power of two: exact
+    if (d.kdiv && c < (d.mode == 0 ? d.CtotW : d.CoutW)) v = v / d.kdiv[c];   // exact
     return v;
 }
 
-// one block per output column m: its power-of-two scale
-__global__ __launch_bounds__(kB) void pack_f16_scale_kernel(const float* __restrict__ w, int mode,
-                                                            int CoutW, int CtotW, int KH, int KW,
-                                                            int c0, int Coutp, int Cinp, int Kpad,
-                                                            const float* __restrict__ kdiv,
-                                                            float* __restrict__ wscale) {
-    const int m = blockIdx.x;
+// f16x3: the block's column m gets its power-of-two scale s_m, max_k |Wsel[k][m]| / s_m in
+// [2^14, 2^15) (1 for an all-zero or non-finite column)
+__device__ __forceinline__ void pack_col_scale(const PackDesc& d, int m) {
     float a = 0.f;
-    for (int k = threadIdx.x; k < Kpad; k += kB)
-        a = fmaxf(a, fabsf(pack_sel(w, mode, CoutW, CtotW, KH, KW, c0, Coutp, Cinp, kdiv, k, m)));
+    for (int k = threadIdx.x; k < d.Kpad; k += kB) a = fmaxf(a, fabsf(pack_sel(d, k, m)));
     for (int o = 32; o > 0; o >>= 1) a = fmaxf(a, __shfl_xor(a, o, 64));
     __shared__ float red[kB / 64];
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
@@ -1385,43 +1331,64 @@ __global__ __launch_bounds__(kB) void pack_f16_scale_kernel(const float* __restr
             // gradient-free dy channels must not get a scale that underflows to 0)
             sc = ldexpf(1.f, max(ex - 1 - 14, -126));
         }
-        wscale[m] = sc;
+        d.wscale[m] = sc;
     }
 }
 
-__global__ __launch_bounds__(kB) void pack_f16x3_kernel(const float* __restrict__ w, int mode,
-                                                        int CoutW, int CtotW, int KH, int KW,
-                                                        int c0, int Coutp, int Cinp, int Kpad,
-                                                        int Mpad, const float* __restrict__ kdiv,
-                                                        const float* __restrict__ wscale,
-                                                        uint16_t* __restrict__ out) {
-    const long i = (long)blockIdx.x * kB + threadIdx.x;   // over Kpad * Mpad
-    if (i >= (long)Kpad * Mpad) return;
-    const int m = (int)(i % Mpad);
-    const int k = (int)(i / Mpad);
-    const float u = pack_sel(w, mode, CoutW, CtotW, KH, KW, c0, Coutp, Cinp, kdiv, k, m) /
-                    wscale[m];
-    uint32_t h, l;
-    s2::split2(u, h, l);
+// The stores: out[kt][g][part][m][e] = part of Wsel[32 kt + 8 g + e][m], (Kpad/32, 4, NP, Mpad, 8).
+// x6: three bf16 parts hi + mid + lo
+__device__ __forceinline__ void pack_store_x6(const PackDesc& d, int k, int m, float v) {
     const int kt = k / 32, g = (k / 8) & 3, e = k & 7;
-    const long base = ((((long)kt * 4 + g) * 2) * Mpad + m) * 8 + e;
-    out[base] = (uint16_t)h;
-    out[base + (long)Mpad * 8] = (uint16_t)l;
+    const uint32_t hb = s3::bfbits(v);
+    const float r1 = v - __uint_as_float(hb << 16);
+    const uint32_t mb = s3::bfbits(r1);
+    const uint32_t lb = s3::bfbits(r1 - __uint_as_float(mb << 16));
+    const long base = ((((long)kt * 4 + g) * 3) * d.Mpad + m) * 8 + e;
+    d.out[base] = (uint16_t)hb;
+    d.out[base + (long)d.Mpad * 8] = (uint16_t)mb;
+    d.out[base + 2l * d.Mpad * 8] = (uint16_t)lb;
+}
+// fp16: one part, the autocast cast of the weight
+__device__ __forceinline__ void pack_store_f16(const PackDesc& d, int k, int m, float v) {
+    const int kt = k / 32, g = (k / 8) & 3, e = k & 7;
+    d.out[(((long)kt * 4 + g) * d.Mpad + m) * 8 + e] = (uint16_t)s2::hbits(v);
+}
+// f16x3 (conv_x6.hip FmtF16): u = v / s_m as h = rne_f16(u), l = rne_f16(u - h)
+__device__ __forceinline__ void pack_store_f16x3(const PackDesc& d, int k, int m, float v) {
+    const int kt = k / 32, g = (k / 8) & 3, e = k & 7;
+    uint32_t h, l;
+    s2::split2(v / d.wscale[m], h, l);
+    const long base = ((((long)kt * 4 + g) * 2) * d.Mpad + m) * 8 + e;
+    d.out[base] = (uint16_t)h;
+    d.out[base + (long)d.Mpad * 8] = (uint16_t)l;
 }
 
-// ---- batched weight packs (tcam_pack_weights): a trainer's repack after every optimizer
-// step is one (fp16) or two (f16x3: column scales, then parts) launches over a table of
-// items instead of one or two launches per conv.  Each block finds its item by binary search
-// over the items' first blocks; the per-item arithmetic is the kernels' above.
-struct PackDesc {
-    const float* w;
-    uint16_t* out;
-    float* wscale;
-    const float* kdiv;
-    int mode, CoutW, CtotW, KH, KW, c0, Coutp, Cinp, Kpad, Mpad;
-    int sb0, pb0;   // the item's first block in the scale / pack launch
-};
+enum PackFmt { kPackX6, kPackF16, kPackF16x3 };
 
+template <PackFmt FMT>
+__device__ __forceinline__ void pack_elem(const PackDesc& d, long i) {   // i over Kpad * Mpad
+    if (i >= (long)d.Kpad * d.Mpad) return;
+    const int m = (int)(i % d.Mpad);
+    const int k = (int)(i / d.Mpad);
+    const float v = pack_sel(d, k, m);
+    if (FMT == kPackX6) pack_store_x6(d, k, m, v);
+    else if (FMT == kPackF16) pack_store_f16(d, k, m, v);
+    else pack_store_f16x3(d, k, m, v);
+}
+
+// one item: the descriptor by value
+__global__ __launch_bounds__(kB) void pack_scale_kernel(PackDesc d) {
+    pack_col_scale(d, blockIdx.x);
+}
+template <PackFmt FMT>
+__global__ __launch_bounds__(kB) void pack_kernel(PackDesc d) {
+    pack_elem<FMT>(d, (long)blockIdx.x * kB + threadIdx.x);
+}
+
+// ---- batched (tcam_pack_weights): a trainer's repack after every optimizer step is one
+// (fp16) or two (f16x3: column scales, then parts) launches over a table of items instead of
+// one or two launches per conv.  Each block finds its item by binary search over the items'
+// first blocks.
 __device__ __forceinline__ int pack_item(const PackDesc* __restrict__ t, int n, int blk,
                                          bool scale) {
     int lo = 0, hi = n - 1;   // the last item whose first block is <= blk
@@ -1436,47 +1403,12 @@ __device__ __forceinline__ int pack_item(const PackDesc* __restrict__ t, int n, 
 __global__ __launch_bounds__(kB) void pack_multi_scale_kernel(const PackDesc* __restrict__ t,
                                                               int n) {
     const PackDesc& d = t[pack_item(t, n, blockIdx.x, true)];
-    const int m = blockIdx.x - d.sb0;
-    float a = 0.f;
-    for (int k = threadIdx.x; k < d.Kpad; k += kB)
-        a = fmaxf(a, fabsf(pack_sel(d.w, d.mode, d.CoutW, d.CtotW, d.KH, d.KW, d.c0, d.Coutp,
-                                    d.Cinp, d.kdiv, k, m)));
-    for (int o = 32; o > 0; o >>= 1) a = fmaxf(a, __shfl_xor(a, o, 64));
-    __shared__ float red[kB / 64];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float v = 0.f;
-        for (int i = 0; i < kB / 64; ++i) v = fmaxf(v, red[i]);
-        float sc = 1.f;
-        if (v > 0.f && isfinite(v)) {
-            int ex = 0;
-            frexpf(v, &ex);
-            sc = ldexpf(1.f, max(ex - 1 - 14, -126));
-        }
-        d.wscale[m] = sc;
-    }
+    pack_col_scale(d, blockIdx.x - d.sb0);
 }
-
-template <bool F16X3>
+template <PackFmt FMT>
 __global__ __launch_bounds__(kB) void pack_multi_kernel(const PackDesc* __restrict__ t, int n) {
     const PackDesc& d = t[pack_item(t, n, blockIdx.x, false)];
-    const long i = (long)(blockIdx.x - d.pb0) * kB + threadIdx.x;   // over Kpad * Mpad
-    if (i >= (long)d.Kpad * d.Mpad) return;
-    const int m = (int)(i % d.Mpad);
-    const int k = (int)(i / d.Mpad);
-    const float v = pack_sel(d.w, d.mode, d.CoutW, d.CtotW, d.KH, d.KW, d.c0, d.Coutp, d.Cinp,
-                             d.kdiv, k, m);
-    const int kt = k / 32, g = (k / 8) & 3, e = k & 7;
-    if (!F16X3) {   // FmtH1: (Kpad/32, 4, 1, Mpad, 8) fp16
-        d.out[(((long)kt * 4 + g) * d.Mpad + m) * 8 + e] = (uint16_t)s2::hbits(v);
-        return;
-    }
-    uint32_t h, l;
-    s2::split2(v / d.wscale[m], h, l);
-    const long base = ((((long)kt * 4 + g) * 2) * d.Mpad + m) * 8 + e;
-    d.out[base] = (uint16_t)h;
-    d.out[base + (long)d.Mpad * 8] = (uint16_t)l;
+    pack_elem<FMT>(d, (long)(blockIdx.x - d.pb0) * kB + threadIdx.x);
 }
 
 }  // namespace
@@ -1541,7 +1473,9 @@ static int bn_relu_bwd(const void* dout, const void* out, const void* y,
             (const uint8_t*)dout, (const uint8_t*)out, (const uint8_t*)y, mean, invstd, P,
             C / 8, part);
     TCAM_CHECK_LAUNCH();
-    bn_bwd_finalize_kernel<<<C, kB, 0, st>>>(part, nchunks, C, dgamma, dbeta, coef);
+    // (no pmax, no scale: the sums alone)
+    bn_bwd_finalize_sc_kernel<<<C, kB, 0, st>>>(part, nchunks, C, P, gamma, invstd, nullptr,
+                                                dgamma, dbeta, coef, nullptr);
     TCAM_CHECK_LAUNCH();
     const long total = P * (C / 8);
     if (amax) {
@@ -1639,13 +1573,11 @@ extern "C" int tcam_bn_relu_bwd_s3s2(const void* dout, const void* out, const vo
 // dy (S3, P pixels x C channels) -> scale[c] (the power of two with amax[c] scale in
 // [2^14, 2^15); 2^126 for an all-zero channel) and dy2, its scaled S2 copy.  amax from
 // tcam_bn_relu_bwd_s3s2, or computed here when `compute` is set (amax zeroed first).
-extern "C" int tcam_dy_scaled_s2(const void* dy, long P, int C, uint32_t* amax, int compute,
-                                 float* scale, void* dy2, void* stream) {
-    TCAM_REQUIRE(dy && amax && scale && dy2 && P > 0 && C > 0 && C % 8 == 0 && C <= 2048);
-    hipStream_t st = as_stream(stream);
+static int dy_scaled(const void* dy, long P, int C, uint32_t* amax, bool compute, float* scale,
+                     void* dy2, hipStream_t st) {
+    TCAM_REQUIRE(C <= 2048);
     const int G = C / 8;
     if (compute) {
-        TCAM_REQUIRE(kB % G == 0);
         TCAM_REQUIRE(hipMemsetAsync(amax, 0, (size_t)C * sizeof(uint32_t), st) == hipSuccess);
         const int per = kB / G;
         const long nb = std::min<long>(1024, (P + per - 1) / per);
@@ -1658,6 +1590,13 @@ extern "C" int tcam_dy_scaled_s2(const void* dy, long P, int C, uint32_t* amax, 
                                                      (uint8_t*)dy2);
     TCAM_CHECK_LAUNCH();
     return TCAM_OK;
+}
+
+extern "C" int tcam_dy_scaled_s2(const void* dy, long P, int C, uint32_t* amax, int compute,
+                                 float* scale, void* dy2, void* stream) {
+    TCAM_REQUIRE(dy && amax && scale && dy2 && P > 0 && C > 0 && C % 8 == 0);
+    TCAM_REQUIRE(!compute || kB % (C / 8) == 0);
+    return dy_scaled(dy, P, C, amax, compute != 0, scale, dy2, as_stream(stream));
 }
 
 // The fused f16x3 BN-ReLU backward (the kernels above): dout S3, y (and out unless the
@@ -1859,19 +1798,43 @@ static void reduce33(const W33Args& a, int splits, int cout_store, float* dw, in
     wgrad33_reduce_kernel<MSUB><<<cdiv(slab, kB), kB, 0, st>>>(a, src, nsum, cout_store, dw, r16);
 }
 
-extern "C" size_t tcam_conv_wgrad_ws_bytes(const tcam_conv_src* srcs, int nsrc, int B,
-                                           int Cout, int Hout, int Wout, int KH, int KW) {
-    int dummy = 0;
-    {
-        W33Args a{};
-        int splits = 0, msub = 0;
-        if (make_w33(srcs, nsrc, B, &dummy, Cout, Hout, Wout, KH, KW, 1, 1, &a, &splits, &msub))
-            return w33_ws_bytes(a, splits, msub);
-    }
+// The generic path (any KH x KW / stride / pad): the fp32 MFMA over 64 x 64 tiles, gradients in
+// layout L, sources in LX; its workspace is the partial slabs.
+static size_t generic_ws_bytes(const tcam_conv_src* srcs, int nsrc, int B, int Cout, int Hout,
+                               int Wout, int KH, int KW) {
     WgArgs a{};
-    int splits = 0;
+    int splits = 0, dummy = 0;
     if (!make_wg(srcs, nsrc, B, &dummy, Cout, Hout, Wout, KH, KW, 0, 0, &a, &splits)) return 0;
     return (size_t)splits * a.ntiles * kWT * kWT * sizeof(float);
+}
+
+template <class L, class LX>
+static int conv_wgrad_generic(const tcam_conv_src* srcs, int nsrc, int B, const void* dy,
+                              int Cout, int Hout, int Wout, int KH, int KW, int pad_h, int pad_w,
+                              int cout_store, float* dw, void* ws, size_t ws_bytes, int r16,
+                              void* stream) {
+    TCAM_REQUIRE(dw && ws && cout_store > 0 && cout_store <= Cout);
+    WgArgs a{};
+    int splits = 0;
+    TCAM_REQUIRE(make_wg(srcs, nsrc, B, dy, Cout, Hout, Wout, KH, KW, pad_h, pad_w, &a, &splits));
+    TCAM_REQUIRE(ws_bytes >= (size_t)splits * a.ntiles * kWT * kWT * sizeof(float));
+    a.part = (float*)ws;
+    hipStream_t st = as_stream(stream);
+    wgrad_kernel<L, LX><<<dim3(a.ntiles, splits), kB, 0, st>>>(a);
+    TCAM_CHECK_LAUNCH();
+    const long total = (long)cout_store * a.Ctot * KH * KW;
+    wgrad_reduce_kernel<<<cdiv(total, kB), kB, 0, st>>>(a, splits, cout_store, dw, r16);
+    TCAM_CHECK_LAUNCH();
+    return TCAM_OK;
+}
+
+extern "C" size_t tcam_conv_wgrad_ws_bytes(const tcam_conv_src* srcs, int nsrc, int B,
+                                           int Cout, int Hout, int Wout, int KH, int KW) {
+    W33Args a{};
+    int splits = 0, msub = 0, dummy = 0;
+    if (make_w33(srcs, nsrc, B, &dummy, Cout, Hout, Wout, KH, KW, 1, 1, &a, &splits, &msub))
+        return w33_ws_bytes(a, splits, msub);
+    return generic_ws_bytes(srcs, nsrc, B, Cout, Hout, Wout, KH, KW);
 }
 
 template <class L, class F>
@@ -1890,23 +1853,13 @@ static int conv_wgrad(const tcam_conv_src* srcs, int nsrc, int B, const void* dy
             hipStream_t st = as_stream(stream);
             if constexpr (F::DPIN != F::XPIN) {
                 // WgF3: the per-channel power-of-two scales of dy (max |dy| s in [2^14, 2^15))
-                TCAM_REQUIRE(Cout <= 2048);
                 uint32_t* amax = reinterpret_cast<uint32_t*>((char*)ws + w33_slab_bytes(a, splits,
                                                                                          msub));
                 float* scale = reinterpret_cast<float*>(amax + Cout);
-                TCAM_REQUIRE(hipMemsetAsync(amax, 0, (size_t)Cout * sizeof(uint32_t), st) ==
-                             hipSuccess);
-                const long P = (long)B * Hout * Wout;
-                const int per = kB / a.Gout;
-                const long nb = std::min<long>(1024, (P + per - 1) / per);
-                dy_amax_kernel<<<(int)nb, kB, 0, st>>>((const uint8_t*)dy, P, a.Gout, amax);
-                TCAM_CHECK_LAUNCH();
-                dy_scale_kernel<<<cdiv(Cout, kB), kB, 0, st>>>(amax, scale, Cout);
-                TCAM_CHECK_LAUNCH();
                 uint8_t* dy2 = reinterpret_cast<uint8_t*>(scale + Cout);
-                dy_to_s2_kernel<<<cdiv(P * a.Gout, kB), kB, 0, st>>>((const uint8_t*)dy, scale,
-                                                                      P * a.Gout, a.Gout, dy2);
-                TCAM_CHECK_LAUNCH();
+                const int rc = dy_scaled(dy, (long)B * Hout * Wout, Cout, amax, true, scale, dy2,
+                                         st);
+                if (rc != TCAM_OK) return rc;
                 a.dy = dy2;
                 a.dscale = scale;
                 a.oflow = oflow;
@@ -1916,15 +1869,8 @@ static int conv_wgrad(const tcam_conv_src* srcs, int nsrc, int B, const void* dy
                 a.dscale = dscale_in;
             }
             if (g_wgrad_fp32 == 0 || F::NP != 3) {
-                // TCAM_WGRAD_PIPE=1: the software-pipelined patch loads (A/B)
-                static const bool pipe = getenv("TCAM_WGRAD_PIPE") &&
-                                         atoi(getenv("TCAM_WGRAD_PIPE")) == 1;
-                if (msub == 1 && pipe)
-                    wgrad33x6_kernel<F, 1, true><<<dim3(a.ntiles, splits), 192, 0, st>>>(a);
-                else if (msub == 1)
+                if (msub == 1)
                     wgrad33x6_kernel<F, 1><<<dim3(a.ntiles, splits), 192, 0, st>>>(a);
-                else if (pipe)
-                    wgrad33x6_kernel<F, 2, true><<<dim3(a.ntiles, splits), 192, 0, st>>>(a);
                 else
                     wgrad33x6_kernel<F, 2><<<dim3(a.ntiles, splits), 192, 0, st>>>(a);
                 TCAM_CHECK_LAUNCH();
@@ -1947,18 +1893,8 @@ static int conv_wgrad(const tcam_conv_src* srcs, int nsrc, int B, const void* dy
         }
     }
     if constexpr (PRESCALED) return TCAM_E_ARG;   // 3x3 / stride 1 / pad 1 only
-    WgArgs a{};
-    int splits = 0;
-    TCAM_REQUIRE(make_wg(srcs, nsrc, B, dy, Cout, Hout, Wout, KH, KW, pad_h, pad_w, &a, &splits));
-    TCAM_REQUIRE(ws_bytes >= (size_t)splits * a.ntiles * kWT * kWT * sizeof(float));
-    a.part = (float*)ws;
-    hipStream_t st = as_stream(stream);
-    wgrad_kernel<L><<<dim3(a.ntiles, splits), kB, 0, st>>>(a);
-    TCAM_CHECK_LAUNCH();
-    const long total = (long)cout_store * a.Ctot * KH * KW;
-    wgrad_reduce_kernel<<<cdiv(total, kB), kB, 0, st>>>(a, splits, cout_store, dw, r16);
-    TCAM_CHECK_LAUNCH();
-    return TCAM_OK;
+    return conv_wgrad_generic<L, L>(srcs, nsrc, B, dy, Cout, Hout, Wout, KH, KW, pad_h, pad_w,
+                                    cout_store, dw, ws, ws_bytes, r16, stream);
 }
 
 extern "C" int tcam_conv_wgrad_s3(const tcam_conv_src* srcs, int nsrc, int B, const void* dy,
@@ -2003,47 +1939,50 @@ extern "C" int tcam_conv_wgrad_s1(const tcam_conv_src* srcs, int nsrc, int B, co
 // (v_mfma_f32_32x32x2_f32: exact products, fp32 sums), deterministic split reduction.
 extern "C" size_t tcam_conv_wgrad_generic_ws_bytes(const tcam_conv_src* srcs, int nsrc, int B,
                                                    int Cout, int Hout, int Wout, int KH, int KW) {
-    WgArgs a{};
-    int splits = 0, dummy = 0;
-    if (!make_wg(srcs, nsrc, B, &dummy, Cout, Hout, Wout, KH, KW, 0, 0, &a, &splits)) return 0;
-    return (size_t)splits * a.ntiles * kWT * kWT * sizeof(float);
+    return generic_ws_bytes(srcs, nsrc, B, Cout, Hout, Wout, KH, KW);
 }
 
 extern "C" int tcam_conv_wgrad_s3s2(const tcam_conv_src* srcs, int nsrc, int B, const void* dy,
                                     int Cout, int Hout, int Wout, int KH, int KW, int pad_h,
                                     int pad_w, int cout_store, float* dw, void* ws,
                                     size_t ws_bytes, void* stream) {
-    TCAM_REQUIRE(dw && ws && cout_store > 0 && cout_store <= Cout);
-    WgArgs a{};
-    int splits = 0;
-    TCAM_REQUIRE(make_wg(srcs, nsrc, B, dy, Cout, Hout, Wout, KH, KW, pad_h, pad_w, &a, &splits));
-    TCAM_REQUIRE(ws_bytes >= (size_t)splits * a.ntiles * kWT * kWT * sizeof(float));
-    a.part = (float*)ws;
-    hipStream_t st = as_stream(stream);
-    wgrad_kernel<LayS3, LayS2><<<dim3(a.ntiles, splits), kB, 0, st>>>(a);
-    TCAM_CHECK_LAUNCH();
-    const long total = (long)cout_store * a.Ctot * KH * KW;
-    wgrad_reduce_kernel<<<cdiv(total, kB), kB, 0, st>>>(a, splits, cout_store, dw, 0);
-    TCAM_CHECK_LAUNCH();
-    return TCAM_OK;
+    return conv_wgrad_generic<LayS3, LayS2>(srcs, nsrc, B, dy, Cout, Hout, Wout, KH, KW, pad_h,
+                                            pad_w, cout_store, dw, ws, ws_bytes, 0, stream);
 }
 
-static int pack_weight(const float* w, void* out, int mode, int CoutW, int CtotW, int KH,
-                       int KW, int c0, int cout_sel, int cin_pad, int h1, void* stream) {
+// The descriptor of one pack from an entry's arguments (tcam_hip.h, tcam_pack_weight_x6).
+static int pack_desc(PackDesc* d, const float* w, void* out, float* wscale, const float* kdiv,
+                     int mode, int CoutW, int CtotW, int KH, int KW, int c0, int cout_sel,
+                     int cin_pad) {
     TCAM_REQUIRE(w && out && CoutW > 0 && CtotW > 0 && KH > 0 && KW > 0);
-    int Coutp, Cinp;
+    *d = PackDesc{w, (uint16_t*)out, wscale, kdiv, mode, CoutW, CtotW, KH, KW, c0};
     if (mode == 0) {   // cin_pad: zero input channels beyond CtotW (the stem's 8-channel image)
-        Coutp = CoutW;
-        Cinp = cin_pad > CtotW ? cin_pad : CtotW;
+        d->Coutp = CoutW;
+        d->Cinp = cin_pad > CtotW ? cin_pad : CtotW;
     } else {
         TCAM_REQUIRE(mode == 1 && c0 >= 0 && cout_sel > 0 && c0 + cout_sel <= CtotW);
-        Coutp = cout_sel;
-        Cinp = cin_pad > CoutW ? cin_pad : CoutW;
+        d->Coutp = cout_sel;
+        d->Cinp = cin_pad > CoutW ? cin_pad : CoutW;
     }
-    int Kpad, Mpad;
-    TCAM_REQUIRE(tcam_conv_x6_weight_dims(KH * KW * Cinp, Coutp, &Kpad, &Mpad) == TCAM_OK);
-    pack_kernel<<<cdiv((long)Kpad * Mpad, kB), kB, 0, as_stream(stream)>>>(
-        w, (uint16_t*)out, mode, CoutW, CtotW, KH, KW, c0, Coutp, Cinp, Kpad, Mpad, h1);
+    return tcam_conv_x6_weight_dims(KH * KW * d->Cinp, d->Coutp, &d->Kpad, &d->Mpad) == TCAM_OK
+               ? TCAM_OK : TCAM_E_ARG;
+}
+
+template <PackFmt FMT>
+static int pack_one(const float* w, void* out, float* wscale, const float* kdiv, int mode,
+                    int CoutW, int CtotW, int KH, int KW, int c0, int cout_sel, int cin_pad,
+                    void* stream) {
+    PackDesc d;
+    const int rc = pack_desc(&d, w, out, wscale, kdiv, mode, CoutW, CtotW, KH, KW, c0, cout_sel,
+                             cin_pad);
+    if (rc != TCAM_OK) return rc;
+    hipStream_t st = as_stream(stream);
+    if (FMT == kPackF16x3) {
+        TCAM_REQUIRE(wscale);
+        pack_scale_kernel<<<d.Mpad, kB, 0, st>>>(d);
+        TCAM_CHECK_LAUNCH();
+    }
+    pack_kernel<FMT><<<cdiv((long)d.Kpad * d.Mpad, kB), kB, 0, st>>>(d);
     TCAM_CHECK_LAUNCH();
     return TCAM_OK;
 }
@@ -2051,39 +1990,22 @@ static int pack_weight(const float* w, void* out, int mode, int CoutW, int CtotW
 extern "C" int tcam_pack_weight_x6(const float* w, void* out, int mode, int CoutW, int CtotW,
                                    int KH, int KW, int c0, int cout_sel, int cin_pad,
                                    void* stream) {
-    return pack_weight(w, out, mode, CoutW, CtotW, KH, KW, c0, cout_sel, cin_pad, 0, stream);
+    return pack_one<kPackX6>(w, out, nullptr, nullptr, mode, CoutW, CtotW, KH, KW, c0, cout_sel,
+                             cin_pad, stream);
 }
 
 extern "C" int tcam_pack_weight_f16(const float* w, void* out, int mode, int CoutW, int CtotW,
                                     int KH, int KW, int c0, int cout_sel, int cin_pad,
                                     void* stream) {
-    return pack_weight(w, out, mode, CoutW, CtotW, KH, KW, c0, cout_sel, cin_pad, 1, stream);
+    return pack_one<kPackF16>(w, out, nullptr, nullptr, mode, CoutW, CtotW, KH, KW, c0, cout_sel,
+                              cin_pad, stream);
 }
 
 extern "C" int tcam_pack_weight_f16x3(const float* w, void* out, float* wscale, int mode,
                                       int CoutW, int CtotW, int KH, int KW, int c0, int cout_sel,
                                       int cin_pad, const float* kdiv, void* stream) {
-    TCAM_REQUIRE(w && out && wscale && CoutW > 0 && CtotW > 0 && KH > 0 && KW > 0);
-    int Coutp, Cinp;
-    if (mode == 0) {   // cin_pad: zero input channels beyond CtotW (the stem's 8-channel image)
-        Coutp = CoutW;
-        Cinp = cin_pad > CtotW ? cin_pad : CtotW;
-    } else {
-        TCAM_REQUIRE(mode == 1 && c0 >= 0 && cout_sel > 0 && c0 + cout_sel <= CtotW);
-        Coutp = cout_sel;
-        Cinp = cin_pad > CoutW ? cin_pad : CoutW;
-    }
-    int Kpad, Mpad;
-    TCAM_REQUIRE(tcam_conv_x6_weight_dims(KH * KW * Cinp, Coutp, &Kpad, &Mpad) == TCAM_OK);
-    hipStream_t st = as_stream(stream);
-    pack_f16_scale_kernel<<<Mpad, kB, 0, st>>>(w, mode, CoutW, CtotW, KH, KW, c0, Coutp, Cinp,
-                                               Kpad, kdiv, wscale);
-    TCAM_CHECK_LAUNCH();
-    pack_f16x3_kernel<<<cdiv((long)Kpad * Mpad, kB), kB, 0, st>>>(
-        w, mode, CoutW, CtotW, KH, KW, c0, Coutp, Cinp, Kpad, Mpad, kdiv, wscale,
-        (uint16_t*)out);
-    TCAM_CHECK_LAUNCH();
-    return TCAM_OK;
+    return pack_one<kPackF16x3>(w, out, wscale, kdiv, mode, CoutW, CtotW, KH, KW, c0, cout_sel,
+                                cin_pad, stream);
 }
 
 // The batched packs.  Items as tcam_pack_weight_f16 (f16x3 == 0: wscale, kdiv unused) or
@@ -2098,30 +2020,12 @@ extern "C" int tcam_pack_weights(const tcam_pack_item* items, int n, int f16x3, 
     long sb = 0, pb = 0;
     for (int i = 0; i < n; ++i) {
         const tcam_pack_item& it = items[i];
-        TCAM_REQUIRE(it.w && it.out && it.CoutW > 0 && it.CtotW > 0 && it.KH > 0 && it.KW > 0);
         TCAM_REQUIRE(!f16x3 || it.wscale);
         PackDesc& d = t[i];
-        d.w = it.w;
-        d.out = (uint16_t*)it.out;
-        d.wscale = it.wscale;
-        d.kdiv = f16x3 ? it.kdiv : nullptr;
-        d.mode = it.mode;
-        d.CoutW = it.CoutW;
-        d.CtotW = it.CtotW;
-        d.KH = it.KH;
-        d.KW = it.KW;
-        d.c0 = it.c0;
-        if (it.mode == 0) {
-            d.Coutp = it.CoutW;
-            d.Cinp = it.cin_pad > it.CtotW ? it.cin_pad : it.CtotW;
-        } else {
-            TCAM_REQUIRE(it.mode == 1 && it.c0 >= 0 && it.cout_sel > 0 &&
-                         it.c0 + it.cout_sel <= it.CtotW);
-            d.Coutp = it.cout_sel;
-            d.Cinp = it.cin_pad > it.CoutW ? it.cin_pad : it.CoutW;
-        }
-        TCAM_REQUIRE(tcam_conv_x6_weight_dims(d.KH * d.KW * d.Cinp, d.Coutp, &d.Kpad, &d.Mpad) ==
-                     TCAM_OK);
+        const int rc = pack_desc(&d, it.w, it.out, it.wscale, f16x3 ? it.kdiv : nullptr, it.mode,
+                                 it.CoutW, it.CtotW, it.KH, it.KW, it.c0, it.cout_sel,
+                                 it.cin_pad);
+        if (rc != TCAM_OK) return rc;
         d.sb0 = (int)sb;
         d.pb0 = (int)pb;
         sb += d.Mpad;
@@ -2146,9 +2050,9 @@ extern "C" int tcam_pack_weights(const tcam_pack_item* items, int n, int f16x3, 
     if (f16x3) {
         pack_multi_scale_kernel<<<(int)sb, kB, 0, st>>>(dt, n);
         TCAM_CHECK_LAUNCH();
-        pack_multi_kernel<true><<<(int)pb, kB, 0, st>>>(dt, n);
+        pack_multi_kernel<kPackF16x3><<<(int)pb, kB, 0, st>>>(dt, n);
     } else {
-        pack_multi_kernel<false><<<(int)pb, kB, 0, st>>>(dt, n);
+        pack_multi_kernel<kPackF16><<<(int)pb, kB, 0, st>>>(dt, n);
     }
     TCAM_CHECK_LAUNCH();
     return TCAM_OK;

@@ -14,7 +14,7 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from . import _lib, ops
+from . import _lib
 from ._lib import check
 
 
@@ -144,20 +144,6 @@ class FlatSGD:
     def _join_side(self) -> None:
         if self._wg_stream is not None:
             torch.cuda.current_stream(self.dev).wait_stream(self._wg_stream)
-
-    def _dy_scaled(self, dy: torch.Tensor, amax: Optional[torch.Tensor] = None):
-        """(dy2, scale): the per-channel power-of-two scaled S2 copy of an S3 gradient (max
-        |dy_c| scale_c in [2^14, 2^15)); amax computed here when not given."""
-        B, H, W, Cc = ops.s3_dims(dy)
-        compute = amax is None
-        if compute:
-            amax = torch.empty(Cc, device=self.dev, dtype=torch.int32)
-        scale = torch.empty(Cc, device=self.dev, dtype=torch.float32)
-        dy2 = ops.lay_empty("s2", B, H, W, Cc, self.dev)
-        check(_lib.load().tcam_dy_scaled_s2(dy.data_ptr(), B * H * W, Cc, amax.data_ptr(),
-                                            1 if compute else 0, scale.data_ptr(),
-                                            dy2.data_ptr(), _stream()), "tcam_dy_scaled_s2")
-        return dy2, scale
 
     # ------------------------------------------------------------- the step
     def _sgd_step(self, dist_scale: float, gate: torch.Tensor) -> None:

@@ -24,7 +24,6 @@ row).
 from __future__ import annotations
 
 import copy
-import ctypes as C
 import os
 from typing import Dict, List, Optional, Sequence
 
@@ -32,13 +31,14 @@ import torch
 import torch.nn.functional as F
 import torch.nn as nn
 
-from . import _lib, crf, ops
-from ._lib import check, tcam_conv_src
+from . import _lib, crf, ops, train_ops
+from ._lib import check
 from .flat_sgd import FlatSGD, _stream
 from .losses import ELB  # noqa: F401  (re-exported: training.ELB)
 from .models import CenterBlock, UnetTCAM
 from .ops import ConvSrc
 from .seeding import prepare_std_cams
+from .train_ops import Grad, pack_weight
 
 # UnetTCAM's eval plans that fold decoder weights / BN
 DECODER_PLANS = ("dec_x6", "dec_f16x3", "dec_amp", "dec")
@@ -369,8 +369,6 @@ class DecoderTrainer(FlatSGD):
         self._crf_stream = None
         self._crf_pre = None    # the next step's lattice, built during this step's backward
         self.wgrad_side = os.environ.get("TCAM_WGRAD_SIDE", "1") != "0"
-        # the fused BN-ReLU backward of the f16x3 step (TCAM_FUSED_BN_BWD=0: three passes)
-        self.fused_bn_bwd = os.environ.get("TCAM_FUSED_BN_BWD", "1") != "0"
         self._wg_stream = None
         self._enc_stream = None
         self._enc_pre = None    # (images, version, plan, feats, event) of prefetch_encoder
@@ -380,7 +378,7 @@ class DecoderTrainer(FlatSGD):
         # activations (conv outputs, BN-ReLU outputs) in S2 on the f16x3 convolutions; the
         # gradients stay S3 and reach the f16x3 MFMA as per-channel scaled S2 copies (the
         # weight gradient divides the scales out in its reduction, the data gradient in its
-        # per-step packed weights; tcam_dy_scaled_s2, tcam_pack_weight_f16x3)
+        # per-step packed weights; train_ops.dy_scaled, train_ops.pack_weight)
         prec = prec or os.environ.get("TCAM_TRAIN_PREC", "f16x3")
         if prec not in ("f16x3", "x6"):
             raise ValueError(f"training precision {prec!r}: 'f16x3' or 'x6'")
@@ -388,6 +386,7 @@ class DecoderTrainer(FlatSGD):
         self.fmt = "amp" if self.amp else ("f16x3" if self.f16 else "x6")  # decoder convs
         self.lay = ops.FMT_LAYOUT[self.fmt]           # and its activation layout
         self.glay = "s1" if self.amp else "s3"        # the gradients' layout
+        self.gfmt = "amp" if self.amp else "x6"       # and the format whose layout that is
         # the 3x3 weight gradients of the fp32-accurate step: f16x3 (dy with per-channel
         # power-of-two scales, three fp16 MFMA products: half x6's work, the same fp64
         # error band) unless TCAM_WGRAD=x6
@@ -454,79 +453,25 @@ class DecoderTrainer(FlatSGD):
             cur = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
         return cur
 
-    def _pack_x6(self, w: torch.Tensor, mode: int, c0: int = 0, sel: int = 0,
-                 cin_pad: int = 0) -> torch.Tensor:
-        cout, ctot, kh, kw = w.shape
-        K, M = (kh * kw * ctot, cout) if mode == 0 else (kh * kw * max(cout, cin_pad), sel)
-        kp, mp = ops.conv_x6_weight_dims(K, M)
-        out = torch.empty((kp // 32, 4, 3, mp, 8), device=self.dev, dtype=torch.bfloat16)
-        check(_lib.load().tcam_pack_weight_x6(w.data_ptr(), out.data_ptr(), mode, cout, ctot, kh,
-                                              kw, c0, sel, cin_pad, _stream()),
-              "tcam_pack_weight_x6")
-        return out
-
-    def _pack(self, w: torch.Tensor, mode: int, c0: int = 0, sel: int = 0,
-              cin_pad: int = 0) -> torch.Tensor:
-        cout, ctot, kh, kw = w.shape
-        if mode == 0:
-            K, M = kh * kw * ctot, cout
-        else:
-            K, M = kh * kw * max(cout, cin_pad), sel
-        kp, mp = ops.conv_x6_weight_dims(K, M)
-        lib = _lib.load()
-        if self.amp:   # autocast's fp16 weight
-            out = torch.empty((kp // 32, 4, 1, mp, 8), device=self.dev, dtype=torch.float16)
-            fn, name = lib.tcam_pack_weight_f16, "tcam_pack_weight_f16"
-        else:
-            out = torch.empty((kp // 32, 4, 3, mp, 8), device=self.dev, dtype=torch.bfloat16)
-            fn, name = lib.tcam_pack_weight_x6, "tcam_pack_weight_x6"
-        check(fn(w.data_ptr(), out.data_ptr(), mode, cout, ctot, kh, kw, c0, sel, cin_pad,
-                 _stream()), name)
-        return out
-
-    def _pack_f16(self, c: _Conv, w: torch.Tensor, mode: int, sel: int = 0,
-                  kdiv: Optional[torch.Tensor] = None):
-        """The f16x3 operand (+ per-column scales) of a trainable conv, packed on the device
-        into the conv's own buffers; mode 1 = the data-gradient operand over the first
-        ``sel`` input channels, divided by ``kdiv`` (dy's per-channel scales)."""
-        cout, ctot, kh, kw = w.shape
-        K, M = (kh * kw * ctot, cout) if mode == 0 else (kh * kw * cout, sel)
-        kp, mp = ops.conv_x6_weight_dims(K, M)
-        attr = ("wx6", "wsc") if mode == 0 else ("wdg", "dsc")
-        wt, sc = getattr(c, attr[0]), getattr(c, attr[1])
-        if wt is None or wt.dtype != torch.float16 or tuple(wt.shape) != (kp // 32, 4, 2, mp, 8):
-            wt = torch.empty((kp // 32, 4, 2, mp, 8), device=self.dev, dtype=torch.float16)
-            sc = torch.empty(mp, device=self.dev, dtype=torch.float32)
-            setattr(c, attr[0], wt)
-            setattr(c, attr[1], sc)
-        check(_lib.load().tcam_pack_weight_f16x3(
-            w.data_ptr(), wt.data_ptr(), sc.data_ptr(), mode, cout, ctot, kh, kw, 0,
-            sel if mode else 0, 0, kdiv.data_ptr() if kdiv is not None else None, _stream()),
-            "tcam_pack_weight_f16x3")
-        return wt, sc
-
     def repack(self):
         """Split operands of every trainable conv from the flat fp32 weights."""
         self._packed_version = self.param_version()
-        if self.f16:
-            # the forward operands now; the data-gradient operands are packed in the
-            # backward, once dy's scales are known
-            for c in self._convs():
-                self._pack_f16(c, c.conv.weight.data, 0)
-            self.seg_dg = self._pack_x6(self.seg.weight.data, 1, 0, self.seg.in_channels,
-                                        cin_pad=8)
-            self.seg_w, self.seg_b = self.seg.weight.data, self.seg.bias.data
-            return
-        for c in self._convs():
-            c.wx6 = self._pack(c.conv.weight.data, 0)
-        for i, (c1, c2) in enumerate(self.blocks):
-            c2.wdg = self._pack(c2.conv.weight.data, 1, 0, c2.ctot)
-            c2.dg_cout = c2.ctot
-            c1.wdg, c1.dg_cout = None, 0     # packed lazily (its slice depends on the input)
-        for c in self.center:
-            c.wdg = None
-        # the seg head's data gradient reads dfcams padded to 8 channels
-        self.seg_dg = self._pack(self.seg.weight.data, 1, 0, self.seg.in_channels, cin_pad=8)
+        fmt = self.fmt
+        for c in self._convs():   # f16x3: into the conv's own buffers
+            c.wx6, c.wsc = pack_weight(c.conv.weight.data, fmt, 0,
+                                       out=(c.wx6, c.wsc) if self.f16 else None)
+        if not self.f16:
+            # the data-gradient operands that need no dy scale (f16x3 packs its own in the
+            # backward, once dy's scales are known)
+            for c1, c2 in self.blocks:
+                c2.wdg, _ = pack_weight(c2.conv.weight.data, fmt, 1, sel=c2.ctot)
+                c2.dg_cout = c2.ctot
+                c1.wdg, c1.dg_cout = None, 0     # packed lazily (its slice depends on the input)
+            for c in self.center:
+                c.wdg = None
+        # the seg head's data gradient reads dfcams padded to 8 channels (S3 on the f16x3 step)
+        self.seg_dg, _ = pack_weight(self.seg.weight.data, self.gfmt, 1,
+                                     sel=self.seg.in_channels, cin_pad=8)
         # the seg head's forward operands (AMP: autocast's fp16 weight and bias)
         if self.amp:
             self.seg_w = self.seg.weight.data.half().float()
@@ -536,117 +481,39 @@ class DecoderTrainer(FlatSGD):
 
     # --------------------------------------------------------------- ops
     def _bn_fwd(self, c: _Conv, y: torch.Tensor):
-        lib = _lib.load()
-        B, H, W, Cc = ops.s3_dims(y)
-        P = B * H * W
-        self._bn_ws = self._ws(self._bn_ws, int(lib.tcam_bn_ws_bytes(P, Cc)), self.dev)
-        mean = torch.empty(Cc, device=self.dev)
-        invstd = torch.empty(Cc, device=self.dev)
-        bn = c.bn
-        lay = self.lay
-        check(getattr(lib, f"tcam_bn_stats_{lay}")(
-            y.data_ptr(), P, Cc, bn.eps, bn.momentum, mean.data_ptr(), invstd.data_ptr(),
-            bn.running_mean.data_ptr(), bn.running_var.data_ptr(), self._bn_ws.data_ptr(),
-            _stream()), f"tcam_bn_stats_{lay}")
-        out = torch.empty_like(y)
-        check(getattr(lib, f"tcam_bn_relu_{lay}")(
-            y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), bn.weight.data_ptr(),
-            bn.bias.data_ptr(), out.data_ptr(), P, Cc, _stream()), f"tcam_bn_relu_{lay}")
-        return out, mean, invstd
+        self._bn_ws = self._ws(self._bn_ws, train_ops.bn_ws_bytes(y), self.dev)
+        mean, invstd = train_ops.bn_stats(y, c.bn, self.lay, self._bn_ws)
+        return train_ops.bn_relu(y, mean, invstd, c.bn, self.lay), mean, invstd
 
-    def _bn_bwd(self, c: _Conv, dout, out, y, mean, invstd):
-        """dy of bn_relu (S3 / S1, the gradients' layout); the f16x3 step returns
-        (dy2, scale): dy's per-channel scaled S2 copy for the f16x3 weight and data
-        gradients (the max |dy| per channel comes out of the backward kernel itself)."""
-        lib = _lib.load()
-        B, H, W, Cc = ops.s3_dims(y)
-        P = B * H * W
-        self._bn_ws = self._ws(self._bn_ws, int(lib.tcam_bn_ws_bytes(P, Cc)), self.dev)
-        if self.f16 and self.fused_bn_bwd:
-            # one fused pass pair: the scaled S2 copy straight out of the backward (the
-            # mask recomputed from y: every decoder BN is a BN-ReLU), DESIGN.md "Training"
-            self._bn_ws = self._ws(self._bn_ws, int(lib.tcam_bn_bwd_scaled_ws_bytes(P, Cc)),
-                                   self.dev)
-            dy2 = ops.lay_empty("s2", B, H, W, Cc, self.dev)
-            scale = torch.empty(Cc, device=self.dev, dtype=torch.float32)
-            check(lib.tcam_bn_relu_bwd_scaled_s3s2(
-                dout.data_ptr(), None, y.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                c.bn.weight.data_ptr(), c.bn.bias.data_ptr(), None, dy2.data_ptr(),
-                scale.data_ptr(), self.g(c.bn.weight).data_ptr(), self.g(c.bn.bias).data_ptr(),
-                P, Cc, self._bn_ws.data_ptr(), _stream()), "tcam_bn_relu_bwd_scaled_s3s2")
-            return dy2, scale
+    def _bn_bwd(self, c: _Conv, dout, out, y, mean, invstd) -> Grad:
+        """The gradient of a decoder BN-ReLU; f16x3 and AMP recompute the mask from y (the
+        f16x3 step gets dy's scaled S2 copy straight out of the backward, DESIGN.md
+        "Training")."""
+        self._bn_ws = self._ws(self._bn_ws, train_ops.bn_ws_bytes(y, self.f16), self.dev)
+        return train_ops.bn_relu_bwd(dout, out, y, mean, invstd, c.bn, self.g(c.bn.weight),
+                                     self.g(c.bn.bias), self.fmt, self._bn_ws,
+                                     masky=self.fmt != "x6")
+
+    def _wgrad(self, srcs, g: Grad, dw: torch.Tensor, cout_store: Optional[int] = None):
+        """3x3 / pad 1 weight gradient of a decoder conv (or the seg head) into ``dw``."""
+        arr = train_ops.conv_srcs(srcs)
+        self._wg_ws = self._ws(self._wg_ws,
+                               train_ops.conv_wgrad_ws_bytes(arr, g, self.fmt, 3, 1), self.dev)
+        train_ops.conv_wgrad(arr, g, dw, self._wg_ws, self.fmt, 3, 1,
+                             wgrad_prec=self.wgrad_prec, cout_store=cout_store)
+
+    def _dgrad(self, c: _Conv, g: Grad, sel: int, H: int, W: int) -> torch.Tensor:
+        """Data gradient of ``c`` w.r.t. its first ``sel`` input channels: the conv of dy with
+        the transposed / rotated weight.  f16x3: packed this step over dy's scales, an S3
+        output; x6 / AMP: the operand cached until the next repack."""
+        w = c.conv.weight.data
         if self.f16:
-            dy = ops.lay_empty("s3", B, H, W, Cc, self.dev)
-            amax = torch.empty(Cc, device=self.dev, dtype=torch.int32)
-            check(lib.tcam_bn_relu_bwd_s3s2(dout.data_ptr(), out.data_ptr(), y.data_ptr(),
-                                            mean.data_ptr(), invstd.data_ptr(),
-                                            c.bn.weight.data_ptr(), dy.data_ptr(),
-                                            self.g(c.bn.weight).data_ptr(),
-                                            self.g(c.bn.bias).data_ptr(), P, Cc,
-                                            self._bn_ws.data_ptr(), amax.data_ptr(), _stream()),
-                  "tcam_bn_relu_bwd_s3s2")
-            return self._dy_scaled(dy, amax)
-        dy = torch.empty_like(y)
-        if self.amp and self.fused_bn_bwd:   # two passes, the mask recomputed from y
-            check(lib.tcam_bn_relu_bwd_fused_s1(
-                dout.data_ptr(), None, y.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                c.bn.weight.data_ptr(), c.bn.bias.data_ptr(), dy.data_ptr(),
-                self.g(c.bn.weight).data_ptr(), self.g(c.bn.bias).data_ptr(), P, Cc,
-                self._bn_ws.data_ptr(), _stream()), "tcam_bn_relu_bwd_fused_s1")
-            return dy
-        name = f"tcam_bn_relu_bwd_{self.lay}"
-        check(getattr(lib, name)(dout.data_ptr(), out.data_ptr(), y.data_ptr(), mean.data_ptr(),
-                                 invstd.data_ptr(), c.bn.weight.data_ptr(), dy.data_ptr(),
-                                 self.g(c.bn.weight).data_ptr(), self.g(c.bn.bias).data_ptr(),
-                                 P, Cc, self._bn_ws.data_ptr(), _stream()), name)
-        return dy
-
-    def _wgrad_s2(self, srcs, dy2: torch.Tensor, dsc: torch.Tensor, dw: torch.Tensor,
-                  cout_store: Optional[int] = None):
-        """3x3 weight gradient of the f16x3 step: S2 sources, dy's scaled S2 copy."""
-        lib = _lib.load()
-        B, Ho, Wo, Cd = ops.s3_dims(dy2)
-        arr = (tcam_conv_src * len(srcs))()
-        for i, s in enumerate(srcs):
-            _, H, W, Cc = ops.s3_dims(s.t)
-            arr[i] = tcam_conv_src(s.t.data_ptr(), Cc, H, W, s.stride, 1 if s.up2 else 0)
-        nb = int(lib.tcam_conv_wgrad_ws_bytes(arr, len(srcs), B, Cd, Ho, Wo, 3, 3))
-        self._wg_ws = self._ws(self._wg_ws, nb, self.dev)
-        check(lib.tcam_conv_wgrad_s2_f16x3(arr, len(srcs), B, dy2.data_ptr(), dsc.data_ptr(), Cd,
-                                           Ho, Wo, 3, 3, 1, 1, cout_store or Cd, dw.data_ptr(),
-                                           self._wg_ws.data_ptr(), self._wg_ws.numel(),
-                                           _stream()), "tcam_conv_wgrad_s2_f16x3")
-
-    def _dgrad_f16(self, c: _Conv, dy2: torch.Tensor, dsc: torch.Tensor, sel: int, H: int,
-                   W: int) -> torch.Tensor:
-        """Data gradient of the f16x3 step w.r.t. the first ``sel`` input channels: the
-        transposed / rotated weight packed this step over dy's scales, the f16x3 conv of
-        dy2, an S3 output."""
-        wt, sc = self._pack_f16(c, c.conv.weight.data, 1, sel, kdiv=dsc)
-        return ops.conv2d_f16x3_s3out([ConvSrc(dy2)], wt, sc, self._zeros(sel), sel, H, W, 3, 1)
-
-    def _wgrad(self, srcs, dy: torch.Tensor, cout: int, k, pad, dw: torch.Tensor,
-               cout_store: Optional[int] = None):
-        lib = _lib.load()
-        B, Ho, Wo, Cd = ops.s3_dims(dy)
-        kh, kw = (k, k) if isinstance(k, int) else k
-        arr = (tcam_conv_src * len(srcs))()
-        for i, s in enumerate(srcs):
-            _, H, W, Cc = ops.s3_dims(s.t)
-            arr[i] = tcam_conv_src(s.t.data_ptr(), Cc, H, W, s.stride, 1 if s.up2 else 0)
-        nb = int(lib.tcam_conv_wgrad_ws_bytes(arr, len(srcs), B, Cd, Ho, Wo, kh, kw))
-        self._wg_ws = self._ws(self._wg_ws, nb, self.dev)
-        args = (arr, len(srcs), B, dy.data_ptr(), Cd, Ho, Wo, kh, kw, pad, pad, cout_store or Cd,
-                dw.data_ptr(), self._wg_ws.data_ptr(), self._wg_ws.numel())
-        if self.wgrad_prec == "f16x3":
-            # (an x beyond the fp16 range sets the f16x3 overflow flag: raised by the next
-            # evaluation's check, ops.check_f16_overflow)
-            name = "tcam_conv_wgrad_s3_f16x3"
-            check(lib.tcam_conv_wgrad_s3_f16x3(*args, ops.f16_overflow_flag(self.dev).data_ptr(),
-                                                _stream()), name)
-        else:
-            name = f"tcam_conv_wgrad_{self.lay}"
-            check(getattr(lib, name)(*args, _stream()), name)
+            c.wdg, c.dsc = pack_weight(w, "f16x3", 1, sel=sel, kdiv=g.scale, out=(c.wdg, c.dsc))
+            return ops.conv2d_f16x3_s3out([ConvSrc(g.op)], c.wdg, c.dsc, self._zeros(sel), sel,
+                                          H, W, 3, 1)
+        if c.wdg is None or c.dg_cout != sel:
+            (c.wdg, _), c.dg_cout = pack_weight(w, self.fmt, 1, sel=sel), sel
+        return ops.conv2d_x6([ConvSrc(g.op)], c.wdg, self._zeros(sel), sel, H, W, 3, 1, False)
 
     # ------------------------------------------------------------ forward
     def forward(self, images: torch.Tensor):
@@ -939,6 +806,7 @@ class DecoderTrainer(FlatSGD):
         B, _, H, W = dF.shape
         x16 = st["dec_out"]
         cin = ops.s3_dims(x16)[3]
+        glay = self.glay
         # seg head: bias grad, weight grad (dy = dfcams padded to 8 channels), data grad
         self._chansum_ws = self._ws(self._chansum_ws,
                                     int(lib.tcam_chansum_ws_bytes(B, 2, H * W)), self.dev)
@@ -947,100 +815,49 @@ class DecoderTrainer(FlatSGD):
         if self.amp:   # the fp16 bias of the autocast seg-head conv: an fp16 gradient
             gb = self.g(self.seg.bias)
             gb.copy_(gb.half().float())
-        if self.f16:
-            return self._backward_f16(dF, st, x16, cin)
-        dF8 = ops.s3_from_nchw(dF, 8, self.fmt)
-        self._side(lambda: self._wgrad([ConvSrc(x16)], dF8, 8, 3, 1,
-                                       self.g(self.seg.weight), cout_store=2), x16, dF8)
+        # every gradient below is a Grad (dy, op, scale): the f16x3 step's reach the weight /
+        # data gradients as their per-channel scaled S2 copies, x6's and AMP's as they are
+        dF8 = ops.s3_from_nchw(dF, 8, self.gfmt)
+        gF = train_ops.dy_scaled(dF8) if self.f16 else Grad(dF8, dF8, None)
+        self._side(lambda: self._wgrad([ConvSrc(x16)], gF, self.g(self.seg.weight),
+                                       cout_store=2), x16, gF.op, gF.scale)
+        # the seg head's data gradient: x6 on dfcams also on the f16x3 step (8 -> 16
+        # channels, cheap)
         dx = ops.conv2d_x6([ConvSrc(dF8)], self.seg_dg, self._zeros(cin), cin, H, W, 3, 1, False)
         for bi in range(len(self.blocks) - 1, -1, -1):
             c1, c2 = self.blocks[bi]
             s = st["blocks"][bi]
             Ho, Wo = s["y1"].shape[1], s["y1"].shape[2]
-            dy2 = self._bn_bwd(c2, dx, s["a2"], s["y2"], s["m2"], s["i2"])
-            self._side(lambda: self._wgrad([ConvSrc(s["a1"])], dy2, c2.cout, 3, 1,
-                                           self.g(c2.conv.weight)), s["a1"], dy2)
-            da1 = ops.conv2d_x6([ConvSrc(dy2)], c2.wdg, self._zeros(c2.ctot), c2.ctot, Ho, Wo,
-                                3, 1, False)
-            dy1 = self._bn_bwd(c1, da1, s["a1"], s["y1"], s["m1"], s["i1"])
-            self._side(lambda: self._wgrad(s["srcs"], dy1, c1.cout, 3, 1,
-                                           self.g(c1.conv.weight)),
-                       dy1, *[q.t for q in s["srcs"]])
+            g2 = self._bn_bwd(c2, dx, s["a2"], s["y2"], s["m2"], s["i2"])
+            self._side(lambda: self._wgrad([ConvSrc(s["a1"])], g2, self.g(c2.conv.weight)),
+                       s["a1"], g2.op, g2.scale)
+            da1 = self._dgrad(c2, g2, c2.ctot, Ho, Wo)
+            g1 = self._bn_bwd(c1, da1, s["a1"], s["y1"], s["m1"], s["i1"])
+            self._side(lambda: self._wgrad(s["srcs"], g1, self.g(c1.conv.weight)),
+                       g1.op, g1.scale, *[q.t for q in s["srcs"]])
             if bi == 0 and not self.center:
                 break   # the encoder is frozen: no gradient below the first block
             # gradient w.r.t. the block input x (first source channels only)
             cx = ops.s3_dims(s["x"])[3]
-            if c1.wdg is None or c1.dg_cout != cx:
-                c1.wdg = self._pack(c1.conv.weight.data, 1, 0, cx)
-                c1.dg_cout = cx
-            dxu = ops.conv2d_x6([ConvSrc(dy1)], c1.wdg, self._zeros(cx), cx, Ho, Wo, 3, 1,
-                                False)
+            dxu = self._dgrad(c1, g1, cx, Ho, Wo)
             h, w = s["hw"]
-            dx = ops.lay_empty(self.lay, B, h, w, cx, self.dev)
+            dx = ops.lay_empty(glay, B, h, w, cx, self.dev)
             if s["resized"] is not None:
-                name = f"tcam_up2_resize_bwd_{self.lay}"
+                name = f"tcam_up2_resize_bwd_{glay}"
                 check(getattr(lib, name)(dxu.data_ptr(), dx.data_ptr(), B, cx, h, w, Ho, Wo,
                                          _stream()), name)
             else:
-                name = f"tcam_up2_bwd_{self.lay}"
+                name = f"tcam_up2_bwd_{glay}"
                 check(getattr(lib, name)(dxu.data_ptr(), dx.data_ptr(), B, cx, h, w, _stream()),
                       name)
         for ci in range(len(self.center) - 1, -1, -1):
             c = self.center[ci]
             xin, y, a, mean, inv = st["center"][ci]
-            dyc = self._bn_bwd(c, dx, a, y, mean, inv)
-            self._side(lambda: self._wgrad([ConvSrc(xin)], dyc, c.cout, 3, 1,
-                                           self.g(c.conv.weight)), xin, dyc)
+            gc = self._bn_bwd(c, dx, a, y, mean, inv)
+            self._side(lambda: self._wgrad([ConvSrc(xin)], gc, self.g(c.conv.weight)),
+                       xin, gc.op, gc.scale)
             if ci > 0:
-                if c.wdg is None:
-                    c.wdg = self._pack(c.conv.weight.data, 1, 0, c.ctot)
-                Hc, Wc = y.shape[1], y.shape[2]
-                dx = ops.conv2d_x6([ConvSrc(dyc)], c.wdg, self._zeros(c.ctot), c.ctot, Hc, Wc,
-                                   3, 1, False)
-
-    def _backward_f16(self, dF: torch.Tensor, st, x16: torch.Tensor, cin: int):
-        """The f16x3 step's backward below the seg-head bias: gradients in S3, each
-        reaching the f16x3 weight / data gradients as its per-channel scaled S2 copy."""
-        lib = _lib.load()
-        B, _, H, W = dF.shape
-        dF8 = ops.s3_from_nchw(dF, 8, "x6")
-        d2, dsc = self._dy_scaled(dF8)
-        self._side(lambda: self._wgrad_s2([ConvSrc(x16)], d2, dsc, self.g(self.seg.weight),
-                                          cout_store=2), x16, d2, dsc)
-        # the seg head's data gradient: x6 on dfcams (S3; 8 -> 16 channels, cheap)
-        dx = ops.conv2d_x6([ConvSrc(dF8)], self.seg_dg, self._zeros(cin), cin, H, W, 3, 1, False)
-        for bi in range(len(self.blocks) - 1, -1, -1):
-            c1, c2 = self.blocks[bi]
-            s = st["blocks"][bi]
-            Ho, Wo = s["y1"].shape[1], s["y1"].shape[2]
-            dy2, sc2 = self._bn_bwd(c2, dx, s["a2"], s["y2"], s["m2"], s["i2"])
-            self._side(lambda: self._wgrad_s2([ConvSrc(s["a1"])], dy2, sc2,
-                                              self.g(c2.conv.weight)), s["a1"], dy2, sc2)
-            da1 = self._dgrad_f16(c2, dy2, sc2, c2.ctot, Ho, Wo)
-            dy1, sc1 = self._bn_bwd(c1, da1, s["a1"], s["y1"], s["m1"], s["i1"])
-            self._side(lambda: self._wgrad_s2(s["srcs"], dy1, sc1, self.g(c1.conv.weight)),
-                       dy1, sc1, *[q.t for q in s["srcs"]])
-            if bi == 0 and not self.center:
-                break   # the encoder is frozen: no gradient below the first block
-            # gradient w.r.t. the block input x (first source channels only)
-            cx = ops.s3_dims(s["x"])[3]
-            dxu = self._dgrad_f16(c1, dy1, sc1, cx, Ho, Wo)
-            h, w = s["hw"]
-            dx = ops.lay_empty("s3", B, h, w, cx, self.dev)
-            if s["resized"] is not None:
-                check(lib.tcam_up2_resize_bwd_s3(dxu.data_ptr(), dx.data_ptr(), B, cx, h, w, Ho,
-                                                 Wo, _stream()), "tcam_up2_resize_bwd_s3")
-            else:
-                check(lib.tcam_up2_bwd_s3(dxu.data_ptr(), dx.data_ptr(), B, cx, h, w, _stream()),
-                      "tcam_up2_bwd_s3")
-        for ci in range(len(self.center) - 1, -1, -1):
-            c = self.center[ci]
-            xin, y, a, mean, inv = st["center"][ci]
-            dyc, scc = self._bn_bwd(c, dx, a, y, mean, inv)
-            self._side(lambda: self._wgrad_s2([ConvSrc(xin)], dyc, scc,
-                                              self.g(c.conv.weight)), xin, dyc, scc)
-            if ci > 0:
-                dx = self._dgrad_f16(c, dyc, scc, c.ctot, y.shape[1], y.shape[2])
+                dx = self._dgrad(c, gc, c.ctot, y.shape[1], y.shape[2])
 
     def all_reduce_and_step(self, gated: bool = False):
         """The shared step; ``gated``: the step is skipped on the device when the

@@ -27,16 +27,17 @@ regrown or shared between differently shaped calls.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Tuple
 
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
-from ._lib import check, tcam_conv_src
-from .cl_training import Stage1Trainer, _p, _stream
+from . import _lib, ops, train_ops
+from ._lib import check
+from .cl_training import Stage1Trainer, _stream
 from .models import STDClassifier
 from .ops import ConvSrc
+from .train_ops import Grad, _p, pack_weight
 
 VGG16 = "vgg16"
 
@@ -148,8 +149,8 @@ class VGG16ClassifierTrainer(Stage1Trainer):
         fp16-rounded biases autocast gives a conv)."""
         self._packed_version = self.param_version()
         for c in self.convs:
-            c.wt, c.wsc = self._pack(c.conv.weight.data, 0, cin_pad=c.cin_pad,
-                                     out=(c.wt, c.wsc))
+            c.wt, c.wsc = pack_weight(c.conv.weight.data, self.fmt, 0, cin_pad=c.cin_pad,
+                                      out=(c.wt, c.wsc))
             if self.amp:
                 if c.bias16 is None:
                     c.bias16 = torch.empty(c.cout, device=self.dev, dtype=torch.float32)
@@ -179,9 +180,9 @@ class VGG16ClassifierTrainer(Stage1Trainer):
         return logits, {"convs": saved, "pooled": pooled, "feat": f}
 
     # ----------------------------------------------------------- backward
-    def _relu_bwd(self, dout: torch.Tensor, a: torch.Tensor, db: torch.Tensor):
-        """(dz, dy2, scale) of one conv's ReLU: dz = dout [a > 0] (S3 / S1), the bias gradient
-        into ``db``; f16x3: dy2 / scale the per-channel scaled S2 copy (AMP: None)."""
+    def _relu_bwd(self, dout: torch.Tensor, a: torch.Tensor, db: torch.Tensor) -> Grad:
+        """The gradient of one conv's ReLU: dz = dout [a > 0] (S3 / S1), the bias gradient into
+        ``db``; f16x3: with its per-channel scaled S2 copy for the MFMA."""
         lib = _lib.load()
         B, H, W, Cc = ops.s3_dims(a)
         P = B * H * W
@@ -191,9 +192,7 @@ class VGG16ClassifierTrainer(Stage1Trainer):
         name = "tcam_relu_bwd_s1" if self.amp else "tcam_relu_bwd_s3s2"
         check(getattr(lib, name)(dout.data_ptr(), a.data_ptr(), dz.data_ptr(), db.data_ptr(),
                                  _p(amax), P, Cc, ws.data_ptr(), ws.numel(), _stream()), name)
-        if self.amp:
-            return dz, None, None
-        return (dz,) + self._dy_scaled(dz, amax)
+        return Grad(dz, dz, None) if self.amp else train_ops.dy_scaled(dz, amax)
 
     def _pool_bwd(self, gout: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
         lib = _lib.load()
@@ -205,45 +204,31 @@ class VGG16ClassifierTrainer(Stage1Trainer):
                                  Wo, _stream()), name)
         return gin
 
-    def _wgrad(self, c: _VConv, x: torch.Tensor, op: torch.Tensor,
-               scale: Optional[torch.Tensor]) -> None:
-        """The 3x3 weight gradient of ``c`` on input ``x`` from the MFMA copy of dy (``op``:
-        dy2 with its ``scale``, or AMP's S1 dz) into the flat gradient buffer."""
-        lib = _lib.load()
+    def _wgrad(self, c: _VConv, x: torch.Tensor, g: Grad) -> None:
+        """The 3x3 weight gradient of ``c`` on input ``x`` into the flat gradient buffer."""
         B, H, W, Cx = ops.s3_dims(x)
-        Cd = c.cout
-        arr = (tcam_conv_src * 1)()
-        arr[0] = tcam_conv_src(x.data_ptr(), Cx, H, W, 1, 0)
-        ws = self._scratch("conv_wgrad", (B, Cx, Cd, H, W),
-                           lib.tcam_conv_wgrad_ws_bytes(arr, 1, B, Cd, H, W, 3, 3))
+        arr = train_ops.conv_srcs([ConvSrc(x)])
+        ws = self._scratch("conv_wgrad", (B, Cx, c.cout, H, W),
+                           train_ops.conv_wgrad_ws_bytes(arr, g, self.fmt, 3, 1))
         gw = self.g(c.conv.weight)
         dw = gw
         if Cx != c.cin:   # the image padded to 8 channels: only the real ones are kept
             if c.dw_pad is None:
-                c.dw_pad = torch.empty((Cd, Cx, 3, 3), device=self.dev, dtype=torch.float32)
+                c.dw_pad = torch.empty((c.cout, Cx, 3, 3), device=self.dev, dtype=torch.float32)
             dw = c.dw_pad
-        if self.amp:
-            check(lib.tcam_conv_wgrad_s1(arr, 1, B, op.data_ptr(), Cd, H, W, 3, 3, 1, 1, Cd,
-                                         dw.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-                  "tcam_conv_wgrad_s1")
-        else:
-            check(lib.tcam_conv_wgrad_s2_f16x3(arr, 1, B, op.data_ptr(), scale.data_ptr(), Cd, H,
-                                               W, 3, 3, 1, 1, Cd, dw.data_ptr(), ws.data_ptr(),
-                                               ws.numel(), _stream()),
-                  "tcam_conv_wgrad_s2_f16x3")
+        train_ops.conv_wgrad(arr, g, dw, ws, self.fmt, 3, 1)
         if dw is not gw:
             gw.copy_(dw[:, :c.cin])
 
-    def _dgrad(self, c: _VConv, op: torch.Tensor, scale: Optional[torch.Tensor], H: int,
-               W: int) -> torch.Tensor:
+    def _dgrad(self, c: _VConv, g: Grad, H: int, W: int) -> torch.Tensor:
         """d loss / d (the input of ``c``): the stride-1 conv of dy's MFMA copy with the
         transposed, rotated weight (divided by dy's scales on the f16x3 path)."""
-        c.dwt, c.dsc = self._pack(c.conv.weight.data, 1, sel=c.cin, kdiv=scale,
-                                  out=(c.dwt, c.dsc))
+        c.dwt, c.dsc = pack_weight(c.conv.weight.data, self.fmt, 1, sel=c.cin, kdiv=g.scale,
+                                   out=(c.dwt, c.dsc))
         zero = self._zeros(c.cin)
         if self.amp:
-            return ops.conv2d_x6([ConvSrc(op)], c.dwt, zero, c.cin, H, W, 3, 1, False)
-        return ops.conv2d_f16x3_s3out([ConvSrc(op)], c.dwt, c.dsc, zero, c.cin, H, W, 3, 1)
+            return ops.conv2d_x6([ConvSrc(g.op)], c.dwt, zero, c.cin, H, W, 3, 1, False)
+        return ops.conv2d_f16x3_s3out([ConvSrc(g.op)], c.dwt, c.dsc, zero, c.cin, H, W, 3, 1)
 
     def backward(self, dlogits: torch.Tensor, st) -> None:
         """Gradients of every parameter into the flat buffer from d loss / d logits."""
@@ -253,10 +238,9 @@ class VGG16ClassifierTrainer(Stage1Trainer):
             x, a = st["convs"][i]
             if c.pool:
                 dout = self._pool_bwd(dout, a)
-            dz, dy2, scale = self._relu_bwd(dout, a, self.g(c.conv.bias))
-            op = dz if self.amp else dy2
-            self._wgrad(c, x, op, scale)
+            g = self._relu_bwd(dout, a, self.g(c.conv.bias))
+            self._wgrad(c, x, g)
             if i == 0:
                 break   # the image needs no gradient
             _, H, W, _ = ops.s3_dims(x)
-            dout = self._dgrad(c, op, scale, H, W)
+            dout = self._dgrad(c, g, H, W)
